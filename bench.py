@@ -12,6 +12,16 @@ distinct).  `--gpus N` shards the 65 536 documents over N ranks in contiguous bl
 fixed, rank r owns documents [r*65536/N, (r+1)*65536/N)); at N=1 the whole 64K-doc batch (25.8 GB of op log) is on one GPU.
 `--docs-per-gpu D` fixes the per-rank share instead (the 8 192-doc shard of round 1 = --docs-per-gpu 8192).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) only sets up, warms up, times the N steps, checks that every log of the last
+step is ok and every document converged, writes the last step's outputs if `--dump-outputs DIR` is given, and prints the result line.
+Everything else — the sustained leg, the launch without admission, the extra legs, the parity guard against the oracle and the CPU
+baseline — runs only with `--full`.
+
+`--dump-outputs DIR` (rank 0) writes what the timed path computed in its last step as float64 .npy files: per replica log its status and
+counts (logs.npy) and its 128-bit digest as four 32-bit words (digests.npy), the device's count of converged documents, and the decoded
+result rows (values, span rows, comment intervals, with per-log offsets) of a seeded sample of documents (sample_*.npy).  The inputs are
+generated from --seed, so two builds run with the same arguments can be compared file for file.
+
 One JSON line on stdout (rank 0):
   roofline.achieved = SURVEY.md §8(d) algorithmic bytes of one launch, B_alg = sum over logs of 32*N + 4*V + 8*S + 16*T + 16
       (N rows of the log, V visible values, S span rows, T = comment-interval rows — what this ABI writes in place of a
@@ -21,9 +31,9 @@ One JSON line on stdout (rank 0):
   roofline.traffic  = HBM bytes per launch from the PMC counters of the same command (profiles/r06_hbm_traffic.json, made by
       tools/pmc_traffic.sh on the GPU box: separate --pmc passes; reads = the L2's read requests by size, cross-checked against
       FETCH_SIZE calibrated as MI355X_MICROARCH.md prescribes; writes = WRITE_SIZE); null when that file does not describe this workload.
-  parity            = --check-docs random documents of the RESIDENT batch checked against the oracle run on the host cores on
+  parity            = (--full) --check-docs random documents of the RESIDENT batch checked against the oracle run on the host cores on
       WHOLE logs (decoded spans, raw rows, digests of the rows the timed launches wrote).
-  cpu_baseline      = the reference's own code (oracle/_ref) on the same sampled logs, one process per core, time-boxed.
+  cpu_baseline      = (--full) the reference's own code (oracle/_ref) on the same sampled logs, one process per core, time-boxed.
 """
 import argparse
 import json
@@ -206,6 +216,63 @@ def load_traffic(n_logs, rows, launch):
     return t
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_DOCS = 64
+
+
+def dump_outputs(out_dir, eng, db, dr, logs, converged_docs, replicas, seed):
+    """What the last step left in the result buffers, as float64 .npy files in out_dir (u64 digests split into exact 32-bit words).
+    Every replica log's status / counts / digest where they fit in half of DUMP_MAX_BYTES (else a seeded sample of the logs, named by
+    logs_index.npy); the result rows of DUMP_SAMPLE_DOCS seeded documents while the whole stays within DUMP_MAX_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_logs = len(logs)
+    rng = np.random.default_rng(seed)
+    per_log = 8 * (1 + 6 + 4)  # index, six counts, four digest words
+    keep = min(n_logs, (DUMP_MAX_BYTES // 2) // per_log)
+    idx = np.arange(n_logs) if keep == n_logs else np.sort(rng.choice(n_logs, size=keep, replace=False))
+    sel = logs[idx]
+    d = sel["digest"].reshape(-1, 2)
+    arrays = {
+        "logs_index": idx.astype(np.float64),
+        "logs": np.stack([sel[k].astype(np.float64) for k in ("status", "n_ops", "n_elems", "n_visible", "n_spans", "n_cintervals")], axis=1),
+        "digests": np.stack([d[:, k] >> np.uint64(sh) & np.uint64(0xFFFFFFFF) for k in (0, 1) for sh in (0, 32)], axis=1).astype(np.float64),
+        "docs_converged": np.array([converged_docs], dtype=np.float64),
+    }
+    budget = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())
+    n_docs = n_logs // replicas
+    docs = np.sort(rng.choice(n_docs, size=min(DUMP_SAMPLE_DOCS, n_docs), replace=False))
+    s_logs, vals, spans, cints, voff, soff, coff = [], [], [], [], [0], [0], [0]
+    for doc in docs:
+        sub = eng.download_range(db, dr, int(doc) * replicas, replicas)
+        v = sub.values.astype(np.float64)
+        s = np.stack([sub.spans["start"], sub.spans["attr"]], axis=1).astype(np.float64)
+        c = np.stack([sub.cintervals["id"], sub.cintervals["start"], sub.cintervals["end"]], axis=1).astype(np.float64)
+        cost = v.nbytes + s.nbytes + c.nbytes + 4 * 8 * replicas
+        if cost > budget:
+            break
+        budget -= cost
+        for r in range(replicas):
+            s_logs.append(int(doc) * replicas + r)
+            vals.append(v[int(sub.value_off[r]):int(sub.value_off[r + 1])])
+            spans.append(s[int(sub.span_off[r]):int(sub.span_off[r + 1])])
+            cints.append(c[int(sub.cint_off[r]):int(sub.cint_off[r + 1])])
+            voff.append(voff[-1] + len(vals[-1]))
+            soff.append(soff[-1] + len(spans[-1]))
+            coff.append(coff[-1] + len(cints[-1]))
+    arrays.update({
+        "sample_logs": np.array(s_logs, dtype=np.float64),
+        "sample_values": np.concatenate(vals) if vals else np.zeros(0),
+        "sample_value_off": np.array(voff, dtype=np.float64),
+        "sample_spans": np.concatenate(spans) if spans else np.zeros((0, 2)),
+        "sample_span_off": np.array(soff, dtype=np.float64),
+        "sample_cintervals": np.concatenate(cints) if cints else np.zeros((0, 3)),
+        "sample_cint_off": np.array(coff, dtype=np.float64),
+    })
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())), "logs": int(keep), "sample_docs": len(s_logs) // replicas}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,7 +294,12 @@ def main():
     ap.add_argument("--host-sync-step", action="store_true", help="the round-1 step: engine on its own stream, a host-side sync between merge and digest check")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (patch-stream replay rate, experimental builds / launch shapes on the same workload)")
     ap.add_argument("--list-cap", type=int, default=1536, help="list elements per replica the generator holds on chip (the longest list of the 65 536 documents of this seed has 1 334: profiles/r04_j_*; the LDS per document decides how many are generated side by side)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: sustained leg, launch without admission, extra legs, parity guard and "
+                                                         "CPU baseline (--no-cpu, --no-extras, --sustain-s, --check-docs and the --cpu-* options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB; rank 0's documents)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -351,10 +423,22 @@ def main():
         elapsed = float(t.item())
     converged_docs = int(conv.item())
 
-    # ---- sustained leg: the same step back to back for >= --sustain-s seconds (is the rate a cold-boost burst?) ----
+    # ---- every log of the last timed step ok, every document converged (the downloads run on the step's stream, after it) ----
+    logs = eng.download_logs(dr, n_logs)
+    assert int(logs["status"].max()) == 0, "a log failed"
+    assert int(logs["n_ops"].sum()) == ops_per_step
+    dg = logs["digest"].reshape(-1, replicas, 2)
+    assert (dg == dg[:, :1, :]).all(), "replicas of a document must converge"
+    assert converged_docs == total_docs, "device count of converged documents disagrees"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        log("writing the last step's outputs to %s" % args.dump_outputs)
+        dumped = dump_outputs(args.dump_outputs, eng, db, dr, logs, converged_docs, replicas, args.seed)
+
+    # ---- sustained leg (--full): the same step back to back for >= --sustain-s seconds (is the rate a cold-boost burst?) ----
     sustained = None
-    log("sustained leg")
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
+        log("sustained leg")
         n_sus = max(args.steps, int(args.sustain_s / max(elapsed / args.steps, 1e-6)) + 1)
         if world > 1:
             t = torch.tensor([n_sus], dtype=torch.int64, device=side)
@@ -378,15 +462,6 @@ def main():
     if stream is not None:
         eng.set_stream(0)
 
-    log("checks")
-    # ---- every log ok, every document converged ----
-    logs = eng.download_logs(dr, n_logs)
-    assert int(logs["status"].max()) == 0, "a log failed"
-    assert int(logs["n_ops"].sum()) == ops_per_step
-    dg = logs["digest"].reshape(-1, replicas, 2)
-    assert (dg == dg[:, :1, :]).all(), "replicas of a document must converge"
-    assert converged_docs == total_docs, "device count of converged documents disagrees"
-
     total_ops_per_step = ops_per_step * world if weak else sum(counts) * gcfg["ops_per_log"]
     if rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -394,7 +469,8 @@ def main():
 
         # ---- parity guard: random documents of the RESIDENT batch against the reference run on the host cores ----
         parity, cpu = None, None
-        if not args.no_cpu:
+        cpu_legs = args.full and not args.no_cpu
+        if cpu_legs:
             rng = np.random.default_rng(args.seed)
             pick = sorted(int(x) for x in rng.choice(n_docs, size=min(args.check_docs, n_docs), replace=False))
             ones, docs_logs = [], []
@@ -428,7 +504,7 @@ def main():
         achieved = alg_bytes / (k_ms * 1e-3)
         # the same launch without the admission phase (PTX_FLAG_NO_ADMISSION), for reference: a second context on the same resident batch
         ms_noadm = None
-        if not args.no_admission:
+        if args.full and not args.no_admission:
             eng2 = Engine(local, flags=abi.FLAG_NO_ELEM_RANK | abi.FLAG_NO_ADMISSION)
             eng2.merge(db, dr)
             eng2.sync()
@@ -437,7 +513,7 @@ def main():
             eng2.close()
         traffic = load_traffic(n_logs, rows, eng.launch_shape(db))
         extras = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             log("extra legs")
             extras = extra_legs(args, n_docs, first_doc, local, max(2, args.steps // 2))
         threads, lds = eng.launch_shape(db)
@@ -494,6 +570,8 @@ def main():
             },
             "without_admission": None if ms_noadm is None else {"kernel_ms": ms_noadm, "ops_per_s_1gpu": ops_per_step / (ms_noadm * 1e-3),
                                                                 "hbm_GBps": alg_bytes / (ms_noadm * 1e-3) / 1e9, "frac": alg_bytes / (ms_noadm * 1e-3) / HBM_PEAK},
+            "full": args.full,  # without --full: sustained, without_admission, extras, parity and cpu_baseline are not measured (null / absent)
+            "outputs": dumped,  # --dump-outputs
             "sustained": sustained,
             "extras": extras,  # tools/bench_extras.py: patch-stream replay rate; experimental builds / launch shapes on the same workload (not `value`)
             "parity": parity,
@@ -504,7 +582,7 @@ def main():
         }
         if sustained is not None:
             sustained["ops_per_s"] = total_ops_per_step * sustained["steps"] / sustained["seconds"]
-        if not args.no_cpu:
+        if cpu_legs:
             if whole is not None:
                 log("waiting for the whole-log CPU leg")
                 cpu = whole.finish()

@@ -1,6 +1,8 @@
 """Shared test plumbing: oracle invocation (node), the host emulation of the kernel logic, comparison."""
 import ctypes as C
 import functools
+import gzip
+import hashlib
 import json
 import os
 import shutil
@@ -88,6 +90,20 @@ def oracle_change(docs_logs, calls, actors, impl="oracle"):
 def _load_golden(name):
     with open(os.path.join(GOLDEN, name)) as f:
         return json.load(f)
+
+
+def inputs_sha16(obj):
+    """Identity of the inputs a fixture of the reference's answers was made for (inputs built here in Python, not stored with it)."""
+    return hashlib.sha256(json.dumps(obj, sort_keys=True).encode("utf-8")).hexdigest()[:16]
+
+
+def wide_envelope_golden():
+    """tests/golden/wide_envelope_ref.json.gz (tests/make_wide_envelope_golden.py): what the type-erased reference answers for the logs of
+    more than 65 535 changes that test_emu_biglog.wide_envelope_docs() and test_emu_change.past_65535_replica() build."""
+    with gzip.open(os.path.join(GOLDEN, "wide_envelope_ref.json.gz"), "rt", encoding="utf-8") as f:
+        g = json.load(f)
+    assert g["impl"] == "ref"
+    return g
 
 
 def batch_struct(b):

@@ -121,16 +121,23 @@ def test_change_on_generated_replicas_matches_the_oracle():
             log += 1
 
 
-@pytest.mark.skipif(not H.have_node(), reason="node (oracle runtime) not installed")
+def past_65535_replica():
+    """A replica log of 65 600 changes, most of them empty, and the two change() calls made on it."""
+    log = [H.mini_doc([])[0]] + [{"actor": "a", "seq": k, "deps": {}, "startOp": 7, "ops": []} for k in range(2, 65601)]
+    calls = [[[{"path": ["text"], "action": "insert", "index": 2, "values": ["x", "y"]}], [{"path": ["text"], "action": "addMark", "markType": "strong", "startIndex": 1, "endIndex": 4}]]]
+    return log, calls
+
+
 def test_change_on_a_replica_past_65535_changes():
     """seq = clock + 1 and deps = the clock are plain numbers (micromerge.ts:314-327): a replica that has made 65 600 changes (most of them empty:
     change() with no ops still bumps seq) makes change 65 601 with the exact values — the made batch then carries the wide column.
-    Expected: the type-erased reference's own change()."""
-    log = [H.mini_doc([])[0]] + [{"actor": "a", "seq": k, "deps": {}, "startOp": 7, "ops": []} for k in range(2, 65601)]
+    Expected: the type-erased reference's own change() (tests/golden/wide_envelope_ref.json.gz)."""
+    log, calls = past_65535_replica()
     batch = wire.encode_docs([[log]])
     assert batch.chg_env_hi is not None
-    calls = [[[{"path": ["text"], "action": "insert", "index": 2, "values": ["x", "y"]}], [{"path": ["text"], "action": "addMark", "markType": "strong", "startIndex": 1, "endIndex": 4}]]]
-    want = H.oracle_change([[log]], calls, ["a"], impl="ref")
+    g = H.wide_envelope_golden()
+    assert g["change_sha16"] == H.inputs_sha16({"log": log, "calls": calls}), "tests/golden/wide_envelope_ref.json.gz was made for another replica: rerun tests/make_wide_envelope_golden.py"
+    want = g["change"]
     ops = wire.encode_input_ops(batch, calls, ["a"])
     res = H.emu_merge(batch, admission=False)  # (admission of such a log is the HBM-staged kernel's: tests/test_emu_biglog.py)
     made, status = H.emu_change(batch, res, ops)

@@ -138,13 +138,13 @@ def test_logs_with_more_than_65535_changes(eng):
     changes of one actor.  Through the C ABI: the wide envelope column goes up with the batch, the census sends these logs to the HBM-staged kernel, every
     change is admitted; failing logs past 65 535 name the reference's error and the row; an ordinary document in the same batch keeps the LDS kernel; a
     resident log that CROSSES 65 535 changes by ptx_batch_append stays valid.  Expected values: the type-erased reference itself."""
-    from test_emu_biglog import wide_envelope_docs
+    from test_emu_biglog import wide_envelope_docs, wide_envelope_expected
 
     docs = wide_envelope_docs()
     names = list(docs)
     small = _load("ptxgen_mini.json")
     all_docs = [docs[k] for k in names] + [d["logs"] for d in small["docs"]]
-    exp = H.oracle_apply([docs[k] for k in names], impl="ref", no_patches=True, timeout=900) + [d["expected"] for d in small["docs"]]
+    exp = wide_envelope_expected(docs) + [d["expected"] for d in small["docs"]]
     batch = wire.encode_docs(all_docs)
     assert batch.chg_env_hi is not None
     res = eng.apply_materialize(batch)

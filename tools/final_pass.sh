@@ -14,12 +14,12 @@ bash tools/pmc_traffic.sh "$TAG" > "$OUT/traffic.log" 2>&1
 cp "gpurun_out/traffic_$TAG/hbm_traffic.json" profiles/r06_hbm_traffic.json
 cp "gpurun_out/traffic_$TAG/hbm_traffic.json" "$OUT/hbm_traffic.json"
 for f in fetch write size; do cp "gpurun_out/traffic_$TAG/$f.txt" "$OUT/pmc_$f.txt" 2>/dev/null; done
-(cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -- python "$ROOT/bench.py" --no-extras > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err")
+(cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -- python "$ROOT/bench.py" --full --no-extras > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err")
 db=$(find "$OUT/prof" -name '*.db' | head -1)
 [ -n "$db" ] && python tools/prof_summary.py "$db" > "$OUT/kernel_stats.txt" 2>&1
 find "$OUT/prof" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
 rm -rf "$OUT/prof"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 for i in 1 2; do python tools/replay_bench.py 2>&1 | tail -1 >> "$OUT/replay.jsonl"; done
 python tools/replay_bench.py --docs 4096 2>&1 | tail -1 >> "$OUT/replay.jsonl"
 python tools/replay_bench.py --ops 2048 2>&1 | tail -1 >> "$OUT/replay.jsonl"

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 rocm-smi --showclocks --showpower > "$OUT/idle.txt" 2>&1
-python bench.py --no-extras --no-cpu --sustain-s 12 > "$OUT/bench.json" 2> "$OUT/bench.err" &
+python bench.py --full --no-extras --no-cpu --sustain-s 12 > "$OUT/bench.json" 2> "$OUT/bench.err" &
 BP=$!
 for i in $(seq 1 60); do
   echo "--- t=$i" >> "$OUT/poll.txt"
