@@ -246,7 +246,8 @@ typedef struct ptx_patch {
 } ptx_patch;
 typedef struct ptx_patch_log {
     uint32_t status;    /* PTX_OK, or the log's merge status (no stream for a log the reference would have thrown on),
-                           or PTX_ERR_CAPACITY (working set beyond the on-chip memory) */
+                           or PTX_ERR_CAPACITY (more records than the room for them: n_patches is then the exact count; a log beyond the bounds of the
+                           replay: 2^26 - 1 list elements, 65 534 comment ops, 65 535 comment ids) */
     uint32_t n_patches; /* records of this log */
 } ptx_patch_log;
 /* Host-side view of the patch streams of a batch: records of log l at patches[patch_off[l] .. patch_off[l] + logs[l].n_patches).
@@ -255,8 +256,8 @@ typedef struct ptx_patches {
     uint32_t n_logs;
     uint32_t launches;          /* launches of the replay kernel it took: 1 (a log that outgrows the guessed capacity continues in an overflow extent; the records are
                                    packed to exact offsets on the device); 2 only when the overflow arena itself ran out */
-    float kernel_ms;            /* duration of the last launch (HIP events) */
-    uint32_t reserved;
+    float kernel_ms;            /* duration of the last replay (HIP events): the launch of the logs whose state fits the LDS and the HBM-state launch together */
+    uint32_t reserved;          /* hbm_logs: the logs the HBM-state kernel replayed (their replay state beyond one CU's LDS, or PTX_FLAG_REPLAY_HBM_STATE) */
     const uint64_t* patch_off;  /* [n_logs + 1] */
     const ptx_patch_log* logs;  /* [n_logs] */
     const ptx_patch* patches;   /* [patch_off[n_logs]] */
@@ -272,6 +273,8 @@ typedef struct ptx_dresult ptx_dresult;  /* result buffers resident in HBM */
 #define PTX_FLAG_NO_ADMISSION 2u /* ignore the Change envelope (chg_*) even when the batch carries it: no seq / deps checks */
 #define PTX_FLAG_REPLAY_LDS_ONLY 8u /* ptx_replay_patches keeps its whole working set in LDS even where it exceeds 5.5 KB per log (by default the per-slot link urls and the
                                       tables of applied ops then live in global memory: four times the logs per CU); tuning / A-B */
+#define PTX_FLAG_REPLAY_HBM_STATE 16u /* ptx_replay_patches replays EVERY log with its state in global scratch (by default only the logs whose state does not fit one
+                                         CU's LDS: that kernel pays a trip to the L2 per state access); tests / measurement */
 #define PTX_FLAG_PAD_GATHER 4u   /* ptx_allgather_digests always takes its padded path (pack, all-gather of max(counts) pairs per rank, compact on the
                                     device) even when every rank holds the same number of logs: same result; lets a one-GPU host exercise that path */
 
@@ -533,8 +536,9 @@ void ptx_host_batch_free(ptx_host_batch* hb);
  * reference has no bound, micromerge.ts:614-672 — is merged in the same ptx_merge call by the HBM-staged kernel (working set in device scratch the
  * library sizes per log, 32-bit indices; an order of magnitude slower per op), up to 2^26 rows and an id keyspace (max counter + 1) x (actors) of 2^30;
  * PTX_ERR_CAPACITY beyond that.  The editor-facing entry points follow (rounds 5-6): ptx_resolve_cursors on a log of any length; ptx_change too (its element list in
- * global scratch where one CU's LDS cannot hold it); ptx_replay_patches while the replay's bitmaps fit one CU's LDS (about 70 000 list elements, any number of
- * rows: a wide build with 32-bit ranks and boundary slots) — PTX_ERR_CAPACITY for a log beyond that. */
+ * global scratch where one CU's LDS cannot hold it); ptx_replay_patches too (a log whose replay state does not fit one CU's LDS is replayed with that state
+ * in global scratch, ptx_patches.reserved counts them; comment ops and comment ids of one log stay within 16-bit indices — 65 534 ops, 65 535 ids —,
+ * PTX_ERR_CAPACITY for a log beyond that). */
 uint32_t ptx_max_ops_per_log(const ptx_ctx* ctx);
 /* Name of the kernel the merge launches (to find it in a rocprofv3 trace): the family's ... */
 const char* ptx_kernel_name(void);

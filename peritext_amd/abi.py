@@ -31,6 +31,7 @@ FLAG_NO_ELEM_RANK = 1
 FLAG_NO_ADMISSION = 2
 FLAG_PAD_GATHER = 4
 FLAG_REPLAY_LDS_ONLY = 8
+FLAG_REPLAY_HBM_STATE = 16  # ptx_replay_patches: every log through the HBM-state kernel (a test and measurement knob)
 COMM_ID_BYTES = 128
 
 PTX_OK = 0
@@ -190,7 +191,7 @@ class ptx_patches(C.Structure):
         ("n_logs", C.c_uint32),
         ("launches", C.c_uint32),
         ("kernel_ms", C.c_float),
-        ("reserved", C.c_uint32),
+        ("reserved", C.c_uint32),  # logs the HBM-state replay kernel took
         ("patch_off", u64p),
         ("logs", C.POINTER(ptx_patch_log)),
         ("patches", C.POINTER(ptx_patch)),

@@ -28,6 +28,7 @@
 #include "merge_core.h"
 #include "biglog_core.h"
 #include "replay_core.h"
+#include "replay_hbm_core.h"
 #include "gen_core.h"
 #include "change_core.h"
 #include "cursor_core.h"
@@ -151,6 +152,13 @@ extern "C" __global__ void __launch_bounds__(PTX_REPLAY_THREADS) ptx_replay_kern
 extern "C" __global__ void __launch_bounds__(PTX_REPLAY_THREADS) ptx_replay_kernel_wide(PtxReplayArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
     if (blockIdx.x < A.n_logs) ptx_replay_log<PTX_REPLAY_THREADS, true, true>(A, blockIdx.x, ptx_lds);
+}
+
+/* the logs whose replay state does not fit the LDS (replay_hbm_core.h): the state in a slice of A.state per log, a fixed 12 KB of static LDS; one wave per log of
+ * A.log_index */
+extern "C" __global__ void __launch_bounds__(PTX_REPLAY_THREADS) ptx_replay_kernel_hbm(PtxReplayHbmArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_hbm_lds[PTX_REPLAY_HBM_LDS_BYTES];
+    if (blockIdx.x < A.n_hbm) ptx_replay_log_hbm<PTX_REPLAY_THREADS>(A, blockIdx.x, ptx_hbm_lds);
 }
 
 /* the records of every log — first its own capacity [cap_off[l], cap_off[l + 1]), then its overflow extent from ext_off[l] — packed to out_off[l]; the logs from
@@ -1957,44 +1965,85 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
         return fail(ctx, PTX_ERR_HIP, std::string("replay set-up: ") + hipGetErrorString(e));
     }
     uint64_t need = 0, need_g = 0;
-    /* round 6: a batch with a log of more than 32 766 list elements or 65 534 rows takes the wide build (32-bit ranks and slots; the slots' high halves come
+    /* Logs whose replay state does not fit one CU's LDS — or every log, PTX_FLAG_REPLAY_HBM_STATE — go to ONE launch of ptx_replay_kernel_hbm over a list of
+     * log indices (replay_hbm_core.h: the state in a slice of global scratch per log); the others take the launch below exactly as before, its shape (need, wide,
+     * gwin) computed over them alone, so a giant neighbour costs them no occupancy.  A log of more than 32 766 elements whose result lacks the slots' high
+     * halves reports PTX_ERR_CAPACITY from either kernel; it is listed for the HBM-state one, which refuses it before it touches anything. */
+    const bool lds_only = (ctx->flags & PTX_FLAG_REPLAY_LDS_ONLY) != 0, no_hi = b->wide_slots && !r->refs_hi;
+    std::vector<uint8_t> to_hbm(L, 0);
+    for (uint32_t l = 0; l < L; ++l) {
+        const bool wide_l = ptx_replay_wants_wide(log_off[l + 1] - log_off[l], hdr[l]);
+        to_hbm[l] = (ctx->flags & PTX_FLAG_REPLAY_HBM_STATE) != 0 || (no_hi && hdr[l].n_ins > 32766u) || ptx_replay_lds_need_hdr(hdr[l], wide_l || !lds_only, wide_l) > ctx->max_lds;
+    }
+    /* round 6: a launch with a log of more than 32 766 list elements or 65 534 rows takes the wide build (32-bit ranks and slots; the slots' high halves come
      * from the merge: r->refs_hi, there whenever the census found such a log) */
     bool wide = false;
-    for (uint32_t l = 0; l < L; ++l) wide = wide || ptx_replay_wants_wide(log_off[l + 1] - log_off[l], hdr[l]);
-    if (wide && b->wide_slots && !r->refs_hi) wide = false; /* (results allocated for another batch: such logs report PTX_ERR_CAPACITY as before) */
+    for (uint32_t l = 0; l < L; ++l) wide = wide || (!to_hbm[l] && ptx_replay_wants_wide(log_off[l + 1] - log_off[l], hdr[l]));
+    if (wide && no_hi) wide = false; /* (results allocated for another batch: such logs report PTX_ERR_CAPACITY as before) */
+    if (wide) /* (a narrow log beside a wide one is replayed by the wide build: the few that fit only the narrow form go with the large ones) */
+        for (uint32_t l = 0; l < L; ++l) to_hbm[l] = to_hbm[l] || ptx_replay_lds_need_hdr(hdr[l], true, true) > ctx->max_lds;
+    std::vector<uint32_t> hbm_logs;
     for (uint32_t l = 0; l < L; ++l) {
+        if (to_hbm[l]) {
+            hbm_logs.push_back(l);
+            continue;
+        }
         need = std::max<uint64_t>(need, ptx_replay_lds_need_hdr(hdr[l], false, wide));
         need_g = std::max<uint64_t>(need_g, ptx_replay_lds_need_hdr(hdr[l], true, wide));
     }
+    const uint32_t n_hbm = (uint32_t)hbm_logs.size(), n_lds = L - n_hbm;
+    out->reserved = n_hbm;
     /* The replay is one wave per log and lives on occupancy.  Above PTX_REPLAY_GWIN_ABOVE bytes of working set the LDS, not the wave slots, bounds the resident
      * logs: the per-slot link urls and the tables of applied mark ops (half of it; read only by the few ops that need them) move to global memory. */
-    const bool gwin = wide || (need > PTX_REPLAY_GWIN_ABOVE && !(ctx->flags & PTX_FLAG_REPLAY_LDS_ONLY));
+    const bool gwin = wide || (need > PTX_REPLAY_GWIN_ABOVE && !lds_only);
     if (gwin) need = need_g;
-    const uint32_t lds_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, ctx->max_lds); /* larger logs report PTX_ERR_CAPACITY */
+    const uint32_t lds_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, ctx->max_lds); /* (the logs of the other launch do not fit it: this one leaves them at once, PTX_ERR_CAPACITY, and the HBM-state launch BEHIND it on the stream writes their records, plogs and extents last) */
     uint16_t* d_win = nullptr;
     uint64_t* d_winoff = nullptr;
     uint32_t* d_first = nullptr;
-    if (gwin) { /* every log's slice of the scratch: what its header says it needs */
+    uint32_t *d_state = nullptr, *d_hidx = nullptr;
+    uint64_t* d_soff = nullptr;
+    auto release_setup = [&]() {
+        (void)ptx_dev_free(d_win);
+        (void)ptx_dev_free(d_winoff);
+        (void)ptx_dev_free(d_first);
+        (void)ptx_dev_free(d_state);
+        (void)ptx_dev_free(d_hidx);
+        (void)ptx_dev_free(d_soff);
+    };
+    if (gwin && n_lds) { /* every log's slice of the scratch: what its header says it needs (nothing for the logs of the other launch) */
         std::vector<uint64_t> woff((size_t)L + 1, 0);
-        for (uint32_t l = 0; l < L; ++l) woff[l + 1] = woff[l] + ptx_replay_win_units_hdr(hdr[l], wide);
+        for (uint32_t l = 0; l < L; ++l) woff[l + 1] = woff[l] + (to_hbm[l] ? 0u : ptx_replay_win_units_hdr(hdr[l], wide));
         e = ptx_dev_malloc((void**)&d_win, 2 * woff[L] + 16);
         if (e == hipSuccess) e = ptx_dev_malloc((void**)&d_winoff, ((size_t)L + 1) * 8);
         if (e == hipSuccess) e = hipMemcpyAsync(d_winoff, woff.data(), ((size_t)L + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* (woff leaves scope) */
         if (e != hipSuccess) { /* (an early return here leaked the offsets already held by `out`, and named an out-of-memory PTX_ERR_HIP) */
-            (void)ptx_dev_free(d_win);
-            (void)ptx_dev_free(d_winoff);
+            release_setup();
             ptx_patches_free(out);
             return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("replay set-up (scratch): ") + hipGetErrorString(e));
+        }
+    }
+    if (n_hbm) { /* the state slices of the HBM-state launch (the kernel zeroes what it needs zeroed) */
+        std::vector<uint64_t> soff((size_t)n_hbm + 1, 0);
+        for (uint32_t k = 0; k < n_hbm; ++k) soff[k + 1] = soff[k] + ptx_replay_hbm_units_hdr(hdr[hbm_logs[k]]);
+        e = ptx_dev_malloc((void**)&d_state, 4 * soff[n_hbm] + 16);
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&d_soff, ((size_t)n_hbm + 1) * 8);
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&d_hidx, (size_t)n_hbm * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_soff, soff.data(), ((size_t)n_hbm + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_hidx, hbm_logs.data(), (size_t)n_hbm * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* (soff leaves scope) */
+        if (e != hipSuccess) {
+            release_setup();
+            ptx_patches_free(out);
+            return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("replay set-up (state scratch): ") + hipGetErrorString(e));
         }
     }
     if (first_row) {
         e = ptx_dev_malloc((void**)&d_first, (size_t)L * 4);
         if (e == hipSuccess) e = hipMemcpyAsync(d_first, first_row, (size_t)L * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) {
-            (void)ptx_dev_free(d_win);
-            (void)ptx_dev_free(d_winoff);
-            (void)ptx_dev_free(d_first);
+            release_setup();
             ptx_patches_free(out);
             return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("replay set-up: ") + hipGetErrorString(e));
         }
@@ -2076,10 +2125,21 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
             A.arena_cap = arena_cap;
             A.ext_off = d_ext;
             (void)hipEventRecord(ctx->ev0, ctx->stream);
-            if (wide) hipLaunchKernelGGL(ptx_replay_kernel_wide, dim3(L), dim3(PTX_REPLAY_THREADS), lds_bytes, ctx->stream, A);
+            if (!n_lds) { /* (every log belongs to the launch below) */
+            } else if (wide) hipLaunchKernelGGL(ptx_replay_kernel_wide, dim3(L), dim3(PTX_REPLAY_THREADS), lds_bytes, ctx->stream, A);
             else if (gwin) hipLaunchKernelGGL(ptx_replay_kernel_gwin, dim3(L), dim3(PTX_REPLAY_THREADS), lds_bytes, ctx->stream, A);
             else hipLaunchKernelGGL(ptx_replay_kernel, dim3(L), dim3(PTX_REPLAY_THREADS), lds_bytes, ctx->stream, A);
             e = hipGetLastError();
+            if (e == hipSuccess && n_hbm) { /* behind it on the stream: the same records / plogs / extents / arena, the logs of hbm_logs */
+                PtxReplayHbmArgs HA;
+                HA.R = A;
+                HA.state = d_state;
+                HA.state_off = d_soff;
+                HA.log_index = d_hidx;
+                HA.n_hbm = n_hbm;
+                hipLaunchKernelGGL(ptx_replay_kernel_hbm, dim3(n_hbm), dim3(PTX_REPLAY_THREADS), 0, ctx->stream, HA);
+                e = hipGetLastError();
+            }
             (void)hipEventRecord(ctx->ev1, ctx->stream);
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h->logs.data(), d_logs, (size_t)L * sizeof(ptx_patch_log), hipMemcpyDeviceToHost, ctx->stream);
@@ -2130,9 +2190,7 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
         release();
     }
     release();
-    (void)ptx_dev_free(d_win);
-    (void)ptx_dev_free(d_winoff);
-    (void)ptx_dev_free(d_first);
+    release_setup();
     if (st != PTX_OK) {
         ptx_patches_free(out);
         return st;

@@ -297,7 +297,7 @@ class Engine:
                 rows = np.ctypeslib.as_array(C.cast(p.patches, C.POINTER(C.c_uint8)), shape=(total * C.sizeof(abi.ptx_patch),)).view(abi.PATCH_DTYPE).copy()
             else:
                 rows = np.zeros(0, dtype=abi.PATCH_DTYPE)
-            return wire.Patches(patch_off=off, logs=logs, patches=rows, kernel_ms=float(p.kernel_ms), launches=int(p.launches))
+            return wire.Patches(patch_off=off, logs=logs, patches=rows, kernel_ms=float(p.kernel_ms), launches=int(p.launches), hbm_logs=int(p.reserved))
         finally:
             self.lib.ptx_patches_free(C.byref(p))
 

@@ -93,7 +93,8 @@ export interface ReplicaHandle {
     /** micromerge.ts:465-477, resolved on the device (ptx_resolve_cursors); RangeError like :804 / :752 */
     getCursor(path: ["text"], index: number): { objectId: OperationId | null; elemId: OperationId }
     resolveCursor(cursor: { objectId?: OperationId | null; elemId: OperationId }): number
-    /** entry c = the Patch[] the reference's applyChange(c-th change) returns */
+    /** entry c = the Patch[] the reference's applyChange(c-th change) returns; a document of any length (beyond about 80 000 list elements the replay keeps its
+     *  state in device memory instead of on chip: slower per op, the same patches) */
     getPatches(): Patch[][]
     /** throws RangeError("List element not found" | …) exactly where the reference's applyChange would have thrown */
     getTextWithFormatting(path: ["text"]): FormatSpanWithText[]

@@ -758,8 +758,9 @@ def generated_tables(n_docs, replicas, n_comments):
 class Patches:
     """Patch streams of a batch (ptx_replay_patches): records of log l = patches[patch_off[l] : patch_off[l] + logs[l].n_patches]."""
 
-    def __init__(self, patch_off, logs, patches, kernel_ms=0.0, launches=1):
+    def __init__(self, patch_off, logs, patches, kernel_ms=0.0, launches=1, hbm_logs=0):
         self.patch_off, self.logs, self.patches, self.kernel_ms, self.launches = patch_off, logs, patches, kernel_ms, launches
+        self.hbm_logs = hbm_logs  # logs replayed with their state in HBM scratch (ptx_patches.hbm_logs): those beyond one CU's LDS
 
     def of_log(self, log):
         b0 = int(self.patch_off[log])
