@@ -38,6 +38,10 @@
  * One 64-thread workgroup (one wave) per log: the replay is sequential in t.  As ONE wave the phases need no s_barrier and
  * no wait for the patches just stored to HBM (nothing this kernel writes there is read back): PTX_SYNC_T is a compiler fence then.
  *
+ * The split: ptx_replay_walk<kThreads, Store> is the replay, from the early-out to the last write of plogs, written ONCE.  Where the state lives is a Store's
+ * business (its surface is described above PtxReplayLdsStore): PtxReplayLdsStore<kGWin, kWide> here keeps it in the LDS and builds ptx_replay_kernel, _gwin and
+ * _wide through ptx_replay_log; PtxReplayHbmStore (replay_hbm_core.h) keeps it in a slice of global scratch and builds ptx_replay_kernel_hbm.
+ *
  * Compiled two ways like merge_core.h (hipcc: the product kernel; g++ -DPTX_EMU: CPU test tooling only).
  */
 #pragma once
@@ -51,7 +55,7 @@ enum { PTX_RK_SKIP = 0, PTX_RK_MAKELIST = 1, PTX_RK_INSERT = 2, PTX_RK_DELETE = 
 struct PtxReplayArgs {
     const uint64_t* log_off;
     const uint64_t* op_id;
-    const uint64_t* ref_a;
+    const uint64_t* ref_a; /* (ref_a, ref_b, side_a, side_b: the batch's columns, filled like PtxMergeArgs' and not read — the rows come resolved from the merge) */
     const uint64_t* ref_b;
     const uint32_t* payload;
     const uint8_t* action;
@@ -140,9 +144,6 @@ struct PtxPatchDst {
 /* one patch record; rows past the capacity (and the extents) are counted, not written.  `open`: the row is one of those asked for (first_row) */
 PTX_DEV void ptx_patch_put(const PtxPatchDst& d, bool open, uint32_t idx, uint32_t row, uint32_t kind, uint32_t a, uint32_t b) {
     if (!open) return;
-#if defined(PTX_REPLAY_EXP) && (PTX_REPLAY_EXP & 2) /* timing experiment only: what the record stores cost */
-    if (idx != 0xFFFFFFFFu) return;
-#endif
     ptx_patch p;
     p.row = row;
     p.kind = kind;
@@ -187,12 +188,198 @@ PTX_DEV uint32_t ptx_spread16(uint32_t x) {
     return x;
 }
 
-/* kGWin: the per-slot urls and the op tables live in global memory (A.win_scratch), read and written past the L1 (workgroup-scope relaxed atomics) with the
- * wave's outstanding stores waited for wherever one lane reads what another has written */
-template <uint32_t kThreads, bool kGWin = false, bool kWide = false>
-PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) {
-    typedef typename PtxSlotT<kWide>::type slot_t;
-    typedef PtxChunkRowT<kWide> PtxChunkRow;
+
+/* ---- the pieces of the walk that touch no replay state ---- */
+/* no stream for this log (the merge's status, or PTX_ERR_CAPACITY: its state has no room here).  ONE lane */
+PTX_DEV void ptx_replay_fail(const PtxReplayArgs& A, uint32_t log, uint32_t status) {
+    ptx_patch_log pl;
+    pl.status = status;
+    pl.n_patches = 0;
+    A.plogs[log] = pl;
+    if (A.ext_off) A.ext_off[3 * (uint64_t)log] = A.ext_off[3 * (uint64_t)log + 1] = ~0ull;
+}
+/* the end of a stream: its count, whether its room held it, where its extents are.  ONE lane */
+PTX_DEV void ptx_replay_finish(const PtxReplayArgs& A, uint32_t log, const PtxReplayHdr* H, uint32_t produced, uint32_t room) {
+    ptx_patch_log pl;
+    pl.status = produced > room ? (uint32_t)PTX_ERR_CAPACITY : (uint32_t)PTX_OK;
+    pl.n_patches = produced;
+    A.plogs[log] = pl;
+    if (A.ext_off) {
+        A.ext_off[3 * (uint64_t)log] = H->ext_cap[0] ? ((uint64_t)H->ext_hi[0] << 32) | H->ext_lo[0] : ~0ull;
+        A.ext_off[3 * (uint64_t)log + 1] = H->ext_cap[1] ? ((uint64_t)H->ext_hi[1] << 32) | H->ext_lo[1] : ~0ull;
+        A.ext_off[3 * (uint64_t)log + 2] = H->ext_cap[0];
+    }
+}
+/* Room for the records, looked after once per chunk of rows (not per record): a log that may outgrow its room within the chunk that starts at row t0 — three
+ * times its record rate so far, at least eight per row — asks for an extent that holds that rate for all the rows still to come; should that run out too, one
+ * sixteen times as generous.  (A chunk that beats even that loses records: PTX_ERR_CAPACITY with the exact count, and the host launches again with exact
+ * capacities.)  Every lane calls it. */
+template <uint32_t kThreads>
+PTX_DEV void ptx_replay_reserve(const PtxReplayArgs& A, PtxReplayHdr* H, uint32_t t0, uint32_t first, uint32_t N, uint32_t npatch, uint32_t& room, uint32_t& ext_left) {
+    uint32_t rate = 3u * (npatch / (t0 > first ? t0 - first + 1u : 1u) + 1u);
+    rate = rate < 8u ? 8u : rate;
+    if (ext_left && t0 + PTX_RCHUNK > first && npatch + rate * PTX_RCHUNK > room) {
+        rate *= ext_left == 2u ? 1u : 16u;
+        const uint64_t want64 = (uint64_t)rate * (N - t0) + 1024u;
+        const uint32_t want = want64 < 0x7FFFFFFFull - room ? (uint32_t)want64 : 0x7FFFFFFFu - room;
+        PTX_LEADER {
+            const unsigned long long at = ptx_atomic_add64(A.arena_next, (unsigned long long)want);
+            const bool ok = at + want <= A.arena_cap;
+            H->ext_ok = ok ? 1u : 0u;
+            if (!ok) (void)ptx_atomic_add64(A.arena_next, 0ull - (unsigned long long)want); /* hand it back: a smaller request of another log may still fit */
+            if (ok) {
+                const uint32_t k = 2u - ext_left;
+                H->ext_cap[k] = want;
+                H->ext_lo[k] = (uint32_t)(A.arena_base + at);
+                H->ext_hi[k] = (uint32_t)((A.arena_base + at) >> 32);
+            }
+        }
+        PTX_SYNC_T();
+        if (PTX_U32(H->ext_ok)) {
+            room += want;
+            ext_left -= 1u;
+        } else {
+            ext_left = 0u; /* the arena is exhausted */
+        }
+        PTX_SYNC_T();
+    }
+}
+/* One word w of a mark op's range: of its defined slots m, those whose patch — up to the next defined slot, or the end of the range — holds a visible char OF THIS
+ * WORD (peritext.ts:269-281): a char of rank r sits between slots 2 r and 2 r + 1, so it belongs to the patch of the last defined slot at or below 2 r.  The chars
+ * (pw: the word of `present` that holds ranks 16 w ..) spread to their even slots; a reversed addition carries every one of them down to the defined slot that
+ * governs it.  What follows the word belongs to its highest defined slot: `open_top` is that slot's bit when it is one of the changed slots ch and no char of the
+ * word speaks for it — the caller then looks beyond the word.  m != 0. */
+PTX_DEV uint32_t ptx_patch_holders(uint32_t pw, uint32_t w, uint32_t range, uint32_t m, uint32_t ch, uint32_t& open_top) {
+    const uint32_t P2 = ptx_spread16((w & 1u) ? pw >> 16 : pw) & range;
+    uint32_t G = P2 & m;
+    const uint32_t Q = P2 & ~m;
+    if (Q) {
+        const uint32_t Dr = ptx_brev(m);
+        G |= ptx_brev((~Dr + ptx_brev(Q)) & Dr);
+    }
+    open_top = ch & ~G & (1u << (31u - (uint32_t)__builtin_clz(m)));
+    return G;
+}
+
+/* workgroup-scope accesses by operand width (the stores below name the array, not the width) */
+PTX_DEV uint16_t ptx_coherent_load(const uint16_t* p) { return ptx_coherent_load16(p); }
+PTX_DEV uint32_t ptx_coherent_load(const uint32_t* p) { return ptx_coherent_load32(p); }
+PTX_DEV uint64_t ptx_coherent_load(const uint64_t* p) { return ptx_coherent_load64(p); }
+PTX_DEV void ptx_coherent_store(uint16_t* p, uint16_t v) { ptx_coherent_store16(p, v); }
+PTX_DEV void ptx_coherent_store(uint32_t* p, uint32_t v) { ptx_coherent_store32(p, v); }
+PTX_DEV void ptx_coherent_store(uint64_t* p, uint64_t v) { ptx_coherent_store64(p, v); }
+
+/* ---- a STORE: where the replay state of one log lives and how it is reached.  ptx_replay_walk below is written over this surface and nothing else:
+ *   kWide / slot_t     ranks, slots and rows of 32 bits (an entry of `tab` is then two words); kTile: words of a mark op's range the LDS holds cw / cnt for at a
+ *                      time (0: the whole range — the tile loop folds away)
+ *   the arrays         present, defined, mb, cadd, ca, cb, cprev reached with ld / st; lurl, tab, ccid, ctail — the ones the gwin build keeps in global
+ *                      memory — with ldw / stw; load_mb: the four words of a PtxMarkBits
+ *   place / reset      take the arrays from the LDS bump or a slice of scratch (false: no room for this log); zero what must start as zero
+ *   rank, present_set  the visible index of a rank; an element appears / disappears
+ *   last_defined_below, next_defined, set_defined    the closest defined slot to the left / to the right inside a range; a slot becomes defined
+ *   op_head, slot_defined, before_read    the waits for the wave's own global stores: at the head of an op, after PTX_DEFINE_SLOT, before a lane reads what
+ *                      another lane stored in an earlier op — each store waits at the ones it needs
+ * No store holds any of the algorithm. ---- */
+/* The state in the LDS (kGWin: the per-slot urls and the op tables in global memory, A.win_scratch, read and written past the L1 — workgroup-scope relaxed atomics
+ * — with the wave's outstanding stores waited for wherever one lane reads what another has written; kWide: the build of 32-bit ranks and slots) */
+template <bool kGWin, bool kWide_>
+struct PtxReplayLdsStore {
+    static constexpr bool kWide = kWide_;
+    static constexpr uint32_t kTile = 0u; /* the whole range at once */
+    typedef typename PtxSlotT<kWide_>::type slot_t;
+    uint16_t* win; /* (kGWin) the log's slice of A.win_scratch */
+    uint32_t nwe, nws;
+    PtxBitWord* present;
+    uint32_t* defined;
+    PtxMarkBits* mb; /* per defined slot: covered by a comment op; the winner of the LWW type is an addMark */
+    uint32_t* lurl;
+    uint64_t* tab;   /* applied LWW mark op: row | start slot << 16 | end of its interval << 32 (the wide build: two words, row | start slot << 32 and the end) */
+    slot_t *ca, *cb; /* comment op: first covered slot, first slot not covered (SLOT_NONE = to the end) */
+    uint16_t* cprev; /* chain of the ops with the same id, latest first from ctail[id] */
+    uint16_t* ccid;  /* comment op: its id */
+    uint16_t* ctail; /* per comment id: the last registered op (the chain of the ops with one id starts here, latest first) */
+    uint32_t* cadd;  /* bit per comment op: it is an addMark */
+
+    PTX_MEM bool place(PtxBump& bp, const PtxReplayArgs&, uint32_t n, uint32_t N, uint32_t Kl, uint32_t Kc, uint32_t Kid) {
+        nwe = (n >> 5) + 2, nws = ((2 * n + 2) >> 5) + 2;
+        present = ptx_alloc<PtxBitWord>(bp, nwe);
+        defined = ptx_alloc<uint32_t>(bp, nws);
+        mb = ptx_alloc<PtxMarkBits>(bp, nws);
+        if (kGWin) {
+            const uint32_t ucols = (2u * (2u * n + 2u) + 7u) & ~7u, tcols = (Kl + 1u + 7u) & ~7u;
+            lurl = (uint32_t*)win;
+            tab = (uint64_t*)(win + ucols);
+            ccid = win + ucols + (kWide ? 8u : 4u) * tcols;
+            ctail = ccid + ((Kc + 1u + 7u) & ~7u);
+        } else {
+            lurl = ptx_alloc<uint32_t>(bp, 2 * n + 2);
+            tab = ptx_alloc<uint64_t>(bp, (kWide ? 2u : 1u) * (Kl + 1));
+            ccid = ptx_alloc<uint16_t>(bp, Kc + 1);
+            ctail = ptx_alloc<uint16_t>(bp, Kid + 1);
+        }
+        ca = ptx_alloc<slot_t>(bp, Kc + 1);
+        cb = ptx_alloc<slot_t>(bp, Kc + 1);
+        cprev = ptx_alloc<uint16_t>(bp, Kc + 1);
+        cadd = ptx_alloc<uint32_t>(bp, (Kc >> 5) + 1);
+        return kWide || (n <= 32766u && N <= 65534u);
+    }
+    template <uint32_t kThreads>
+    PTX_MEM void reset(uint32_t Kc) {
+        PTX_FOR(w, nwe) {
+            PtxBitWord z;
+            z.bits = 0;
+            z.pre = 0;
+            present[w] = z;
+        }
+        PTX_FOR(w, nws) {
+            defined[w] = 0;
+            PtxMarkBits z;
+            z.ac = z.on[0] = z.on[1] = z.on[2] = 0;
+            mb[w] = z;
+        }
+        PTX_FOR(c, (Kc >> 5) + 1) cadd[c] = 0;
+    }
+    template <class T> PTX_MEM T ld(const T* p) const { return *p; }
+    template <class T> PTX_MEM void st(T* p, T v) const { *p = v; }
+    template <class T> PTX_MEM T ldw(const T* p) const { return kGWin ? ptx_coherent_load(p) : *p; }
+    template <class T> PTX_MEM void stw(T* p, T v) const {
+        if (kGWin) ptx_coherent_store(p, v);
+        else *p = v;
+    }
+    PTX_MEM PtxMarkBits load_mb(uint32_t w) const { return mb[w]; } /* (one 16-byte LDS access) */
+    PTX_MEM void store_mb(uint32_t w, const PtxMarkBits& v) const { mb[w] = v; }
+    PTX_MEM void op_head() const {}
+    PTX_MEM void slot_defined() const {}
+    PTX_MEM void before_read() const {
+        if (kGWin) ptx_global_stores_done();
+    }
+    PTX_MEM uint32_t rank(uint32_t pos) const { return ptx_bitrank(present, pos); }
+    template <uint32_t kThreads>
+    PTX_MEM void present_set(uint32_t r, bool on) const { /* every lane: the prefix of every word above the rank follows */
+        PTX_FOR(w, nwe) {
+            if (w == (r >> 5)) present[w].bits = on ? present[w].bits | (1u << (r & 31)) : present[w].bits & ~(1u << (r & 31));
+            else if (w > (r >> 5)) present[w].pre += on ? 1u : 0xFFFFFFFFu;
+        }
+    }
+    PTX_MEM uint32_t last_defined_below(uint32_t lim) const { return ptx_last_set_below(defined, lim); } /* slot + 1; every lane calls it */
+    /* first defined slot of the range [slot_a, lim) in the words after w (w < whi = (lim + 31) >> 5), else lim.  Any lane */
+    PTX_MEM uint32_t next_defined(uint32_t w, uint32_t slot_a, uint32_t lim, uint32_t whi) const {
+        for (uint32_t v = w + 1u; v < whi; ++v) {
+            const uint32_t mm = defined[v] & ptx_span_mask_in(slot_a, lim, v);
+            if (mm) return (v << 5) + (uint32_t)__builtin_ctz(mm);
+        }
+        return lim;
+    }
+    PTX_MEM void set_defined(uint32_t s) const { defined[s >> 5] |= 1u << (s & 31u); } /* ONE lane */
+};
+
+/* ---- the replay of one log: PTX_RCHUNK rows are resolved in parallel, then applied one at a time (the rows come resolved from the merge: no element index
+ * here).  One wave; `S`: a store whose place() has not run yet; lds_bytes: what the bump allocator may take of `lds` ---- */
+template <uint32_t kThreads, class Store>
+PTX_DEV void ptx_replay_walk(const PtxReplayArgs& A, uint32_t log, uint8_t* lds, uint32_t lds_bytes, Store& S) {
+    typedef typename Store::slot_t slot_t;
+    typedef PtxChunkRowT<Store::kWide> PtxChunkRow;
+    constexpr bool kWide = Store::kWide;
     const uint32_t SLOT_NONE = kWide ? 0xFFFFFFFFu : (uint32_t)PTX_SLOT_NONE;
     PtxReplayHdr* H = (PtxReplayHdr*)lds;
     const uint64_t base = A.log_off[log];
@@ -214,20 +401,13 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
 
     const uint32_t merge_status = A.res[log].status;
     if (merge_status != PTX_OK || N == 0) { /* the reference threw somewhere in this log: no stream (the status says why) */
-        PTX_LEADER {
-            ptx_patch_log pl;
-            pl.status = merge_status;
-            pl.n_patches = 0;
-            A.plogs[log] = pl;
-            if (A.ext_off) A.ext_off[3 * (uint64_t)log] = A.ext_off[3 * (uint64_t)log + 1] = ~0ull;
-        }
+        PTX_LEADER { ptx_replay_fail(A, log, merge_status); }
         return;
     }
     const ptx_log_hdr hd = A.log_hdr[log];
     const uint32_t n = hd.n_ins, Kc = hd.n_mark[PTX_MARK_COMMENT];
     const uint32_t Kid = Kc ? hd.n_comment_ids : 0u; /* id space of the document's comments as this log has seen it */
     const uint32_t K = hd.n_mark[0] + hd.n_mark[1] + hd.n_mark[2] + hd.n_mark[3];
-    const uint32_t nwe = (n >> 5) + 2, nws = ((2 * n + 2) >> 5) + 2;
     /* tables of the applied LWW mark ops per type (0 strong, 1 em, 2 link), in application order */
     const uint32_t Kl = K - Kc;
     const uint32_t toff[3] = {0u, hd.n_mark[PTX_MARK_STRONG], hd.n_mark[PTX_MARK_STRONG] + hd.n_mark[PTX_MARK_EM]};
@@ -235,154 +415,67 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
     PtxBump bp;
     bp.base = lds;
     bp.off = (uint32_t)ptx_a16(sizeof(PtxReplayHdr));
-    bp.cap = A.lds_bytes;
+    bp.cap = lds_bytes;
     bp.high = bp.off;
     bp.overflow = false;
-    PtxBitWord* present = ptx_alloc<PtxBitWord>(bp, nwe);
-    uint32_t* defined = ptx_alloc<uint32_t>(bp, nws);
-    PtxMarkBits* mb = ptx_alloc<PtxMarkBits>(bp, nws); /* per defined slot: covered by a comment op; the winner of the LWW type is an addMark */
-    /* per word of a mark op's range: the changed slots -> the slots that open a record; their count -> its prefix */
-    uint32_t* cw = ptx_alloc<uint32_t>(bp, nws + 1);
-    uint32_t* cnt = ptx_alloc<uint32_t>(bp, nws + 1);
-    uint32_t* lurl;
-    uint64_t* tab;   /* applied LWW mark op: row | start slot << 16 | end of its interval << 32 (the wide build: two words, row | start slot << 32 and the end) */
-    uint16_t* ccid;  /* comment op: its id */
-    uint16_t* ctail; /* per comment id: the last registered op (the chain of the ops with one id starts here, latest first) */
-    if (kGWin) {
-        uint16_t* g = A.win_scratch + A.win_off[log];
-        const uint32_t ucols = (2u * (2u * n + 2u) + 7u) & ~7u, tcols = (Kl + 1u + 7u) & ~7u;
-        lurl = (uint32_t*)g;
-        tab = (uint64_t*)(g + ucols);
-        ccid = g + ucols + (kWide ? 8u : 4u) * tcols;
-        ctail = ccid + ((Kc + 1u + 7u) & ~7u);
-    } else {
-        lurl = ptx_alloc<uint32_t>(bp, 2 * n + 2);
-        tab = ptx_alloc<uint64_t>(bp, (kWide ? 2u : 1u) * (Kl + 1));
-        ccid = ptx_alloc<uint16_t>(bp, Kc + 1);
-        ctail = ptx_alloc<uint16_t>(bp, Kid + 1);
-    }
-#define PTX_G_LD16(p_) (kGWin ? ptx_coherent_load16(p_) : *(p_))
-#define PTX_G_ST16(p_, v_) do { if (kGWin) ptx_coherent_store16((p_), (uint16_t)(v_)); else *(p_) = (uint16_t)(v_); } while (0)
-#define PTX_G_LD32(p_) (kGWin ? ptx_coherent_load32(p_) : *(p_))
-#define PTX_G_LD64(p_) (kGWin ? ptx_coherent_load64(p_) : *(p_))
-#define PTX_G_ST64(p_, v_) do { if (kGWin) ptx_coherent_store64((p_), (uint64_t)(v_)); else *(p_) = (uint64_t)(v_); } while (0)
-#define PTX_G_ST32(p_, v_) do { if (kGWin) ptx_coherent_store32((p_), (uint32_t)(v_)); else *(p_) = (uint32_t)(v_); } while (0)
-#if defined(PTX_REPLAY_EXP) && (PTX_REPLAY_EXP & 1) /* timing experiment only (wrong results possible): what the waits for the wave's outstanding stores cost */
-#define PTX_G_FENCE() do { } while (0)
-#else
-#define PTX_G_FENCE() do { if (kGWin) ptx_global_stores_done(); } while (0)
-#endif
+    const bool placed = S.place(bp, A, n, N, Kl, Kc, Kid);
     /* the next PTX_RCHUNK rows, resolved in parallel (element lookups, boundary slots) before they are replayed in order */
     PtxChunkRow* c_row = ptx_alloc<PtxChunkRow>(bp, PTX_RCHUNK);
-    uint8_t* c_kind = ptx_alloc<uint8_t>(bp, PTX_RCHUNK);  /* PTX_RK_* | mark type << 4 | addMark << 6 */
-    slot_t* ca = ptx_alloc<slot_t>(bp, Kc + 1);           /* comment op: first covered slot */
-    slot_t* cb = ptx_alloc<slot_t>(bp, Kc + 1);           /*             first slot not covered (SLOT_NONE = to the end) */
-    uint16_t* cprev = ptx_alloc<uint16_t>(bp, Kc + 1);    /* chain of the ops with the same id, latest first from ctail[id] */
-    uint32_t* cadd = ptx_alloc<uint32_t>(bp, (Kc >> 5) + 1); /* bit per comment op: it is an addMark */
-    if (bp.overflow || (!kWide && (n > 32766u || N > 65534u)) || n > 0x03FFFFFFu || Kc > 65534u || Kid > 65535u) {
-        PTX_LEADER {
-            ptx_patch_log pl;
-            pl.status = PTX_ERR_CAPACITY;
-            pl.n_patches = 0;
-            A.plogs[log] = pl;
-            if (A.ext_off) A.ext_off[3 * (uint64_t)log] = A.ext_off[3 * (uint64_t)log + 1] = ~0ull;
-        }
+    uint8_t* c_kind = ptx_alloc<uint8_t>(bp, PTX_RCHUNK); /* PTX_RK_* | mark type << 4 | addMark << 6 */
+    /* per word of (a tile of) a mark op's range: the changed slots -> the slots that open a record; their count -> its prefix */
+    const uint32_t ntile = Store::kTile ? Store::kTile : ((2 * n + 2) >> 5) + 3;
+    uint32_t* cw = ptx_alloc<uint32_t>(bp, ntile);
+    uint32_t* cnt = ptx_alloc<uint32_t>(bp, ntile);
+    if (!placed || bp.overflow || n > 0x03FFFFFFu || Kc > 65534u || Kid > 65535u) { /* (comment-op indices and ids stay 16 bits wide in every build) */
+        PTX_LEADER { ptx_replay_fail(A, log, PTX_ERR_CAPACITY); }
         return;
     }
 
-    /* ---- set-up (the rows come resolved from the merge: no element index here) ---- */
-    PTX_FOR(w, nwe) {
-        PtxBitWord z;
-        z.bits = 0;
-        z.pre = 0;
-        present[w] = z;
-    }
-    PTX_FOR(w, nws) {
-        defined[w] = 0;
-        PtxMarkBits z;
-        z.ac = z.on[0] = z.on[1] = z.on[2] = 0;
-        mb[w] = z;
-    }
-    PTX_FOR(c, Kid + 1) PTX_G_ST16(&ctail[c], PTX_CHAIN_NONE);
-    PTX_FOR(c, (Kc >> 5) + 1) cadd[c] = 0;
+    /* ---- set-up ---- */
+    PTX_FOR(c, Kid + 1) S.stw(&S.ctail[c], (uint16_t)PTX_CHAIN_NONE);
+    S.template reset<kThreads>(Kc);
     PTX_LEADER {
         H->tmp = 0;
         H->ext_cap[0] = H->ext_cap[1] = 0;
     }
     PTX_SYNC_T();
     /* the wave's own counters: the same value in every lane */
-    uint32_t npatch = 0, ncom = 0, nvis = 0;
+    uint32_t npatch = 0, ncom = 0;
     uint32_t ntab[3] = {0u, 0u, 0u};
     uint64_t maxop[3] = {0ull, 0ull, 0ull}; /* largest opId applied so far per LWW type */
 
-#ifndef PTX_REPLAY_EXP
-#define PTX_REPLAY_EXP 0 /* timing experiments only (wrong results): bits switch parts of the step off */
-#endif
-#define PTX_VIS_AT(s_) ptx_bitrank(present, ((uint32_t)(s_) + 1u) >> 1) /* visible index at a boundary slot */
-    /* Room for the records, looked after once per chunk of rows (not per record): a log that may outgrow its room within the chunk — three times its record
-     * rate so far, at least eight per row — asks for an extent that holds that rate for all the rows still to come; should that run out too, one sixteen times
-     * as generous.  (A chunk that beats even that loses records: PTX_ERR_CAPACITY with the exact count, and the host launches again with exact capacities.) */
-#define PTX_RESERVE(t_)                                                                                        \
-    do {                                                                                                       \
-        uint32_t rate_ = 3u * (npatch / ((t_) > first ? (t_) - first + 1u : 1u) + 1u);                         \
-        rate_ = rate_ < 8u ? 8u : rate_;                                                                       \
-        if (ext_left && (t_) + PTX_RCHUNK > first && npatch + rate_ * PTX_RCHUNK > room) {                     \
-            rate_ *= ext_left == 2u ? 1u : 16u;                                                                \
-            const uint64_t want64_ = (uint64_t)rate_ * (N - (t_)) + 1024u;                                     \
-            const uint32_t want_ = want64_ < 0x7FFFFFFFull - room ? (uint32_t)want64_ : 0x7FFFFFFFu - room;    \
-            PTX_LEADER {                                                                                       \
-                const unsigned long long at_ = ptx_atomic_add64(A.arena_next, (unsigned long long)want_);      \
-                const bool ok_ = at_ + want_ <= A.arena_cap;                                                   \
-                H->ext_ok = ok_ ? 1u : 0u;                                                                     \
-                if (!ok_) (void)ptx_atomic_add64(A.arena_next, 0ull - (unsigned long long)want_); /* hand it back: a smaller request of another log may still fit */ \
-                if (ok_) {                                                                                     \
-                    const uint32_t k_ = 2u - ext_left;                                                         \
-                    H->ext_cap[k_] = want_;                                                                    \
-                    H->ext_lo[k_] = (uint32_t)(A.arena_base + at_);                                            \
-                    H->ext_hi[k_] = (uint32_t)((A.arena_base + at_) >> 32);                                    \
-                }                                                                                              \
-            }                                                                                                  \
-            PTX_SYNC_T();                                                                                      \
-            if (PTX_U32(H->ext_ok)) {                                                                          \
-                room += want_;                                                                                 \
-                ext_left -= 1u;                                                                                \
-            } else {                                                                                           \
-                ext_left = 0u; /* the arena is exhausted */                                                    \
-            }                                                                                                  \
-            PTX_SYNC_T();                                                                                      \
-        }                                                                                                      \
-    } while (0)
+#define PTX_VIS_AT(s_) S.rank(((uint32_t)(s_) + 1u) >> 1) /* visible index at a boundary slot */
     /* make slot s_ a defined one: its state is that of the closest defined slot to the left (peritext.ts:176) */
 #define PTX_DEFINE_SLOT(s_)                                                                     \
     do {                                                                                        \
-        if (!((PTX_U32(defined[(s_) >> 5]) >> ((s_)&31u)) & 1u)) {                              \
-            const uint32_t l1_ = (PTX_REPLAY_EXP & 8) ? 0u : PTX_U32(ptx_last_set_below(defined, (s_))); /* slot + 1, the same in every lane */ \
+        if (!((PTX_U32(S.ld(&S.defined[(s_) >> 5])) >> ((s_)&31u)) & 1u)) {                     \
+            const uint32_t l1_ = PTX_U32(S.last_defined_below(s_)); /* slot + 1, the same in every lane */ \
             PTX_LEADER {                                                                        \
                 const uint32_t bit_ = 1u << ((s_)&31u), ws_ = (s_) >> 5;                        \
-                if (l1_) { /* (one 16-byte read of the neighbour's word, one of the slot's own, one write) */ \
+                if (l1_) { /* (one read of the neighbour's word, one of the slot's own, one write) */ \
                     const uint32_t l_ = l1_ - 1u, lb_ = l_ & 31u;                               \
-                    const PtxMarkBits src_ = mb[l_ >> 5];                                       \
-                    PtxMarkBits own_ = (l_ >> 5) == ws_ ? src_ : mb[ws_];                       \
+                    const PtxMarkBits src_ = S.load_mb(l_ >> 5);                                \
+                    PtxMarkBits own_ = (l_ >> 5) == ws_ ? src_ : S.load_mb(ws_);                \
                     if ((src_.ac >> lb_) & 1u) own_.ac |= bit_;                                 \
                     if ((src_.on[0] >> lb_) & 1u) own_.on[0] |= bit_;                           \
                     if ((src_.on[1] >> lb_) & 1u) own_.on[1] |= bit_;                           \
                     if ((src_.on[2] >> lb_) & 1u) own_.on[2] |= bit_;                           \
-                    mb[ws_] = own_;                                                             \
+                    S.store_mb(ws_, own_);                                                      \
                     if ((src_.on[2] >> lb_) & 1u) {                                             \
-                        PTX_G_FENCE(); /* (global urls) the stores of the ops before have landed */ \
-                        PTX_G_ST32(&lurl[s_], PTX_G_LD32(&lurl[l_]));                           \
+                        S.before_read(); /* the url stores of the ops before have landed */     \
+                        S.stw(&S.lurl[s_], S.ldw(&S.lurl[l_]));                                 \
                     }                                                                           \
                 }                                                                               \
-                defined[ws_] |= bit_;                                                           \
+                S.set_defined(s_);                                                              \
             }                                                                                   \
+            S.slot_defined(); /* the next search, the passes of the op read what this lane stored */ \
             PTX_SYNC_T();                                                                       \
         }                                                                                       \
     } while (0)
-    /* ---- the replay: PTX_RCHUNK rows are resolved in parallel, then applied one at a time ---- */
 #pragma nounroll
     for (uint32_t t0 = 0; t0 < N; t0 += PTX_RCHUNK) {
     const uint32_t chunk_n = N - t0 < PTX_RCHUNK ? N - t0 : PTX_RCHUNK;
-    PTX_RESERVE(t0);
+    ptx_replay_reserve<kThreads>(A, H, t0, first, N, npatch, room, ext_left);
     PTX_FOR(i, chunk_n) {
         const uint32_t tt = t0 + i, a_ = action[tt];
         uint32_t kind = PTX_RK_SKIP, va = SLOT_NONE, vb = SLOT_NONE;
@@ -414,6 +507,9 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
             }
             kind = PTX_RK_MARK | ((uint32_t)mark_type[tt] << 4) | (a_ == PTX_ACT_ADDMARK ? 64u : 0u);
         }
+        /* (ranks and slots index the state: one beyond the header's element count — a header that understates it — skips the row instead of writing outside) */
+        if ((kind == PTX_RK_INSERT || kind == PTX_RK_DELETE) && va >= n) kind = PTX_RK_SKIP;
+        if ((kind & 15u) == PTX_RK_MARK && ((va != SLOT_NONE && va > 2u * n + 1u) || (vb != SLOT_NONE && vb > 2u * n + 1u))) kind = PTX_RK_SKIP;
         c_kind[i] = (uint8_t)kind;
         PtxChunkRow cr;
         cr.id = op_id[tt];
@@ -429,42 +525,41 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
         const bool open = t >= first;  /* the rows before `first` count records (npatch) but write none ... */
         if (t == first) npatch = 0u;   /* ... and the count starts again at the first row asked for */
         const uint32_t kindb = PTX_U32(c_kind[ci]); /* (one LDS address: the same in every lane) */
-        uint32_t kind = kindb & 15u;
-        if ((PTX_REPLAY_EXP & 256) && kind == PTX_RK_MARK) kind = PTX_RK_SKIP;
-        if ((PTX_REPLAY_EXP & 512) && (kind == PTX_RK_INSERT || kind == PTX_RK_DELETE)) kind = PTX_RK_SKIP;
+        const uint32_t kind = kindb & 15u;
         if (kind == PTX_RK_MAKELIST) {
             PTX_LEADER { ptx_patch_put(dst, open, npatch, t, PTX_PATCH_MAKELIST, 0u, 0u); }
             npatch += 1u;
         } else if (kind == PTX_RK_INSERT) {
+            S.op_head();
             const uint32_t r = PTX_U32(c_row[ci].a);
-            const uint32_t l1 = (PTX_REPLAY_EXP & 32) ? 0u : PTX_U32(ptx_last_set_below(defined, 2u * r)); /* slot + 1 */
+            const uint32_t l1 = PTX_U32(S.last_defined_below(2u * r)); /* slot + 1 */
             const uint32_t p0 = npatch;
             uint32_t attr = 0;
             bool coms = false;
-            if (l1) { /* the marks of the closest defined slot to the left (every lane computes them: LDS broadcasts, one url load) */
+            if (l1) { /* the marks of the closest defined slot to the left (every lane computes them: broadcasts, one url load) */
                 const uint32_t l = l1 - 1u;
                 const uint32_t lw = l >> 5, lb = l & 31u;
-                const PtxMarkBits st = mb[lw]; /* (one 16-byte read) */
+                const PtxMarkBits st = S.load_mb(lw);
                 if ((PTX_U32(st.on[0]) >> lb) & 1u) attr |= PTX_ATTR_STRONG;
                 if ((PTX_U32(st.on[1]) >> lb) & 1u) attr |= PTX_ATTR_EM;
                 if ((PTX_U32(st.on[2]) >> lb) & 1u) {
-                    PTX_G_FENCE();
-                    attr |= PTX_ATTR_LINK | (PTX_U32(PTX_G_LD32(&lurl[l])) & PTX_ATTR_ID_MASK);
+                    S.before_read();
+                    attr |= PTX_ATTR_LINK | (PTX_U32(S.ldw(&S.lurl[l])) & PTX_ATTR_ID_MASK);
                 }
                 coms = (PTX_U32(st.ac) >> lb) & 1u;
                 if (coms) attr |= PTX_ATTR_COMMENT;
             }
-            PTX_LEADER { ptx_patch_put(dst, open, p0, t, PTX_PATCH_INSERT, ptx_bitrank(present, r), attr); }
+            PTX_LEADER { ptx_patch_put(dst, open, p0, t, PTX_PATCH_INSERT, S.rank(r), attr); }
             uint32_t extra = 0;
             if (coms) {
                 const uint32_t l = l1 - 1u;
-                PTX_G_FENCE();
+                S.before_read();
                 PTX_FOR(kc, ncom) {
-                    if (ptx_bittest(cadd, kc) && ca[kc] <= l && l < cb[kc]) {
+                    if (((S.ld(&S.cadd[kc >> 5]) >> (kc & 31u)) & 1u) && S.ld(&S.ca[kc]) <= l && l < S.ld(&S.cb[kc])) {
                         bool last = true; /* no later-applied covering op of the same id: the chain of the id, latest first, down to this op */
-                        const uint32_t id = PTX_G_LD16(&ccid[kc]);
-                        for (uint32_t y = PTX_G_LD16(&ctail[id]); y != kc && y != PTX_CHAIN_NONE; y = cprev[y])
-                            if (ca[y] <= l && l < cb[y]) {
+                        const uint32_t id = S.ldw(&S.ccid[kc]);
+                        for (uint32_t y = S.ldw(&S.ctail[id]); y != kc && y != PTX_CHAIN_NONE; y = S.ld(&S.cprev[y]))
+                            if (S.ld(&S.ca[y]) <= l && l < S.ld(&S.cb[y])) {
                                 last = false;
                                 break;
                             }
@@ -476,29 +571,22 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
                 PTX_SYNC_T();
                 PTX_LEADER { H->tmp = 0; }
             }
-            /* the element is visible from now on */
-            if (!(PTX_REPLAY_EXP & 64)) PTX_FOR(w, nwe) {
-                if (w == (r >> 5)) present[w].bits |= 1u << (r & 31);
-                else if (w > (r >> 5)) present[w].pre += 1;
-            }
+            S.template present_set<kThreads>(r, true); /* the element is visible from now on */
             npatch = p0 + 1u + extra;
-            nvis += 1u;
             PTX_SYNC_T();
         } else if (kind == PTX_RK_DELETE) {
+            S.op_head();
             const uint32_t r = PTX_U32(c_row[ci].a);
-            const bool was = (PTX_U32(present[r >> 5].bits) >> (r & 31)) & 1u;
+            const bool was = (PTX_U32(S.ld(&S.present[r >> 5].bits)) >> (r & 31)) & 1u;
             if (was) {
-                    PTX_LEADER { ptx_patch_put(dst, open, npatch, t, PTX_PATCH_DELETE, ptx_bitrank(present, r), 1u); }
+                PTX_LEADER { ptx_patch_put(dst, open, npatch, t, PTX_PATCH_DELETE, S.rank(r), 1u); }
                 npatch += 1u;
-                nvis -= 1u;
                 PTX_SYNC_T();
-                if (!(PTX_REPLAY_EXP & 64)) PTX_FOR(w, nwe) {
-                    if (w == (r >> 5)) present[w].bits &= ~(1u << (r & 31));
-                    else if (w > (r >> 5)) present[w].pre -= 1;
-                }
+                S.template present_set<kThreads>(r, false);
                 PTX_SYNC_T();
             }
         } else if (kind == PTX_RK_MARK) {
+            S.op_head();
             const uint32_t ty = (kindb >> 4) & 3u;
             const bool add = (kindb & 64u) != 0u;
             const PtxChunkRow cr = c_row[ci];
@@ -514,199 +602,176 @@ PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) 
             if (slot_b != SLOT_NONE) PTX_DEFINE_SLOT(slot_b); /* inherits the state BEFORE this op from inside the range */
             /* the words of [slot_a, lim) */
             const uint32_t lim = slot_b != SLOT_NONE ? slot_b : 2u * n;
-            const uint32_t wlo = slot_a >> 5, whi = (lim + 31u) >> 5, nw = whi > wlo && lim > slot_a && !(PTX_REPLAY_EXP & 128) ? whi - wlo : 0u;
+            const uint32_t wlo = slot_a >> 5, whi = (lim + 31u) >> 5, nw_all = whi > wlo && lim > slot_a ? whi - wlo : 0u;
             const uint32_t my_id = PTX_U32(cr.pay);
             const uint64_t my_op = ((uint64_t)PTX_U32((uint32_t)(cr.id >> 32)) << 32) | PTX_U32((uint32_t)cr.id);
             /* the defined slots of the range in word w_ */
 #define PTX_RANGE_MASK(w_) (ptx_span_mask_in(slot_a, lim, (w_))) /* wlo <= w_ < whi */
-            /* first defined slot of the range in the words after w_, else the end of the range */
-#define PTX_NEXT_AFTER_WORD(w_, out_)                                  \
-    uint32_t out_ = lim;                                               \
-    for (uint32_t v_ = (w_) + 1u; v_ < whi; ++v_) {                    \
-        const uint32_t mm_ = defined[v_] & PTX_RANGE_MASK(v_);         \
-        if (mm_) {                                                     \
-            out_ = (v_ << 5) + (uint32_t)__builtin_ctz(mm_);           \
-            break;                                                     \
-        }                                                              \
-    }
-            /* word wi_ = w_: of the changed slots ch_ (defined slots m_ of the range) keep those whose patch — up to the next defined slot, or the end of the
-             * range — holds a visible char (peritext.ts:269-281): a char of rank r sits between slots 2 r and 2 r + 1, so it belongs to the patch of the last
-             * defined slot at or below 2 r.  Chars spread to their even slots; a reversed addition carries every one of them down to the defined slot that
-             * governs it; what follows the word belongs to its highest defined slot. */
+            /* word wi_ = w_: of the changed slots ch_ (defined slots m_ of the range) keep those whose patch holds a visible char: ptx_patch_holders for the
+             * chars of the word itself; what follows the word — up to the next defined slot, or the end of the range — belongs to its highest defined slot */
 #define PTX_FINISH_WORD(wi_, w_, m_, ch_)                                                                               \
     do {                                                                                                                \
         uint32_t R_ = 0;                                                                                                \
-        if ((ch_) && !(PTX_REPLAY_EXP & 16)) {                                                                          \
-            const uint32_t pw_ = present[(w_) >> 1].bits;                                                               \
-            const uint32_t P2_ = ptx_spread16(((w_)&1u) ? pw_ >> 16 : pw_) & PTX_RANGE_MASK(w_);                        \
-            uint32_t G_ = P2_ & (m_);                                                                                   \
-            const uint32_t Q_ = P2_ & ~(m_);                                                                            \
-            if (Q_) {                                                                                                   \
-                const uint32_t Dr_ = ptx_brev(m_);                                                                      \
-                G_ |= ptx_brev((~Dr_ + ptx_brev(Q_)) & Dr_);                                                            \
-            }                                                                                                           \
-            const uint32_t top_ = 31u - (uint32_t)__builtin_clz(m_);                                                    \
-            if ((((ch_) & ~G_) >> top_) & 1u) {                                                                         \
-                PTX_NEXT_AFTER_WORD(w_, nx_)                                                                            \
-                if (nx_ > (((w_) + 1u) << 5) && PTX_VIS_AT(nx_) > ptx_bitrank(present, ((w_) + 1u) << 4)) G_ |= 1u << top_; \
+        if (ch_) {                                                                                                      \
+            uint32_t open_top_;                                                                                         \
+            uint32_t G_ = ptx_patch_holders(S.ld(&S.present[(w_) >> 1].bits), (w_), PTX_RANGE_MASK(w_), (m_), (ch_), open_top_); \
+            if (open_top_) {                                                                                            \
+                const uint32_t nx_ = S.next_defined((w_), slot_a, lim, whi);                                            \
+                if (nx_ > (((w_) + 1u) << 5) && PTX_VIS_AT(nx_) > S.rank(((w_) + 1u) << 4)) G_ |= open_top_;            \
             }                                                                                                           \
             R_ = (ch_) & G_;                                                                                            \
         }                                                                                                               \
         cw[wi_] = R_;                                                                                                   \
         cnt[wi_] = ptx_popc(R_);                                                                                        \
     } while (0)
+            const bool lww = ty != PTX_MARK_COMMENT;
+            const uint32_t li = ty == PTX_MARK_STRONG ? 0u : ty == PTX_MARK_EM ? 1u : 2u; /* (LWW types) */
+            /* compareOpIds (counter, then actor: the op ids keep that order): this op loses at the slots an applied op of its type with a larger id covers */
+            const bool fast = lww && my_op > maxop[li];
+            const bool per_slot = lww && li == 2u && add; /* the url of every slot the op wins is stored; where the link was on, it decides "changed" */
             uint32_t y0 = PTX_CHAIN_NONE; /* (comments) the last registered op of this op's id */
-            if (ty != PTX_MARK_COMMENT) {
-                const uint32_t li = ty == PTX_MARK_STRONG ? 0u : ty == PTX_MARK_EM ? 1u : 2u;
-                /* compareOpIds (counter, then actor: the op ids keep that order): this op loses at the slots an applied op of its type with a larger id covers */
-                const bool fast = my_op > maxop[li];
-                if (!fast) {
-                    PTX_FOR(wi, nw) cw[wi] = 0u;
-                    PTX_G_FENCE();
-                    PTX_SYNC_T();
-                    PTX_FOR(e, ntab[li]) {
-                        const uint64_t ent = PTX_G_LD64(&tab[(kWide ? 2u : 1u) * (toff[li] + e)]);
-                        if (op_id[kWide ? (uint32_t)ent : (uint32_t)ent & 0xFFFFu] > my_op) {
-                            const uint32_t ya = kWide ? (uint32_t)(ent >> 32) : (uint32_t)(ent >> 16) & 0xFFFFu;
-                            const uint32_t yl = kWide ? (uint32_t)PTX_G_LD64(&tab[2u * (toff[li] + e) + 1u]) : (uint32_t)(ent >> 32);
-                            const uint32_t v0 = (ya >> 5) > wlo ? ya >> 5 : wlo, v1 = ((yl + 31u) >> 5) < whi ? (yl + 31u) >> 5 : whi;
-                            for (uint32_t v = v0; v < v1; ++v) ptx_atomic_or(&cw[v - wlo], ptx_span_mask(ya, yl, v));
-                        }
-                    }
-                    PTX_SYNC_T();
-                }
-                const bool per_slot = li == 2u && add; /* the url of every slot the op wins is stored; where the link was on, it decides "changed" */
-                PTX_FOR(wi, nw) {
-                    const uint32_t w = wlo + wi;
-                    const uint32_t m = defined[w] & PTX_RANGE_MASK(w);
-                    const uint32_t upd = fast ? m : m & ~cw[wi];
-                    const uint32_t old = mb[w].on[li];
-                    if (upd) mb[w].on[li] = add ? old | upd : old & ~upd;
-                    if (per_slot) {
-                        cw[wi] = upd & ~old; /* (the two together: the slots the op wins) */
-                        cnt[wi] = upd & old;
-                    } else {
-                        const uint32_t ch = upd & (add ? ~old : old);
-                        PTX_FINISH_WORD(wi, w, m, ch);
-                    }
-                }
-                if (per_slot) {
-                    PTX_G_FENCE();
-                    PTX_SYNC_T();
-                    const uint32_t my_url = my_id & PTX_ATTR_ID_MASK;
-                    PTX_FOR(j, nw << 5) {
-                        const uint32_t wi = j >> 5, bit = j & 31u;
-                        const bool both = (cnt[wi] >> bit) & 1u; /* the link was on: changed iff the urls differ */
-                        if (both || ((cw[wi] >> bit) & 1u)) { /* (a lane only ever sets ITS bit of cw, and only where `both`: the test reads what the pass before wrote) */
-                            const uint32_t s = ((wlo + wi) << 5) + bit;
-                            if (both && (PTX_G_LD32(&lurl[s]) & PTX_ATTR_ID_MASK) != my_url) ptx_atomic_or(&cw[wi], 1u << bit);
-                            PTX_G_ST32(&lurl[s], my_id);
-                        }
-                    }
-                    PTX_SYNC_T();
-                    PTX_FOR(wi, nw) {
-                        const uint32_t w = wlo + wi;
-                        const uint32_t m = defined[w] & PTX_RANGE_MASK(w);
-                        const uint32_t ch = cw[wi];
-                        PTX_FINISH_WORD(wi, w, m, ch);
-                    }
-                }
-                /* the op joins the table of its type */
-                PTX_LEADER {
-                    if (kWide) {
-                        PTX_G_ST64(&tab[2u * (toff[li] + ntab[li])], (uint64_t)t | ((uint64_t)slot_a << 32));
-                        PTX_G_ST64(&tab[2u * (toff[li] + ntab[li]) + 1u], (uint64_t)lim);
-                    } else {
-                        PTX_G_ST64(&tab[toff[li] + ntab[li]], (uint64_t)t | ((uint64_t)slot_a << 16) | ((uint64_t)lim << 32));
-                    }
-                }
-                ntab[li] += 1u;
-                if (fast) maxop[li] = my_op;
-            } else {
-                /* comments: the last-applied covering op with this id decides (this op is not registered yet): per word, the id's chain latest first */
-                PTX_G_FENCE();
-                y0 = my_id < Kid ? PTX_U32(PTX_G_LD16(&ctail[my_id])) : (uint32_t)PTX_CHAIN_NONE;
-                PTX_FOR(wi, nw) {
-                    const uint32_t w = wlo + wi;
-                    const uint32_t m = defined[w] & PTX_RANGE_MASK(w);
-                    uint32_t und = m, onm = 0;
-                    for (uint32_t y = y0; y != PTX_CHAIN_NONE && und; y = cprev[y]) {
-                        const uint32_t c = ptx_span_mask(ca[y], cb[y], w) & und;
-                        if (ptx_bittest(cadd, y)) onm |= c;
-                        und &= ~c;
-                    }
-                    const uint32_t any = mb[w].ac;
-                    const uint32_t ch = add ? m & ~onm : m & (onm | ~any); /* remove on no comment key: undefined -> [] */
-                    if (m) mb[w].ac = any | m;
-                    PTX_FINISH_WORD(wi, w, m, ch);
-                }
+            if (!lww) {
+                S.before_read();
+                y0 = my_id < Kid ? PTX_U32(S.ldw(&S.ctail[my_id])) : (uint32_t)PTX_CHAIN_NONE;
             }
-            PTX_SYNC_T();
-            const uint32_t P = ptx_scan_excl<uint32_t, 1, kThreads>(cnt, nw, H->scan_tmp);
-            const uint32_t p0 = npatch;
-            if (P) {
-                PTX_FOR(wi, nw) {
-                    uint32_t R = cw[wi];
-                    if (R) {
-                        const uint32_t w = wlo + wi;
-                        const uint32_t m = defined[w] & PTX_RANGE_MASK(w);
-                        uint32_t o = p0 + cnt[wi];
-                        while (R) {
-                            const uint32_t b = (uint32_t)__builtin_ctz(R);
-                            R &= R - 1u;
-                            const uint32_t above = m & ptx_bits_from(b + 1u);
-                            uint32_t nxt;
-                            if (above) {
-                                nxt = (w << 5) + (uint32_t)__builtin_ctz(above);
-                            } else {
-                                PTX_NEXT_AFTER_WORD(w, nx)
-                                nxt = nx;
+            uint32_t prun = npatch;
+            /* the range, Store::kTile words at a time (0: all of it at once): every pass over one tile, its records behind those of the tiles before */
+            uint32_t tw = 0;
+#pragma nounroll
+            do {
+                const uint32_t w0 = wlo + tw, nw = Store::kTile && nw_all - tw > Store::kTile ? Store::kTile : nw_all - tw;
+                if (lww) {
+                    if (!fast) {
+                        PTX_FOR(wi, nw) cw[wi] = 0u;
+                        S.before_read();
+                        PTX_SYNC_T();
+                        PTX_FOR(e, ntab[li]) {
+                            const uint64_t ent = S.ldw(&S.tab[(kWide ? 2u : 1u) * (toff[li] + e)]);
+                            if (op_id[kWide ? (uint32_t)ent : (uint32_t)ent & 0xFFFFu] > my_op) {
+                                const uint32_t ya = kWide ? (uint32_t)(ent >> 32) : (uint32_t)(ent >> 16) & 0xFFFFu;
+                                const uint32_t yl = kWide ? (uint32_t)S.ldw(&S.tab[2u * (toff[li] + e) + 1u]) : (uint32_t)(ent >> 32);
+                                const uint32_t v0 = (ya >> 5) > w0 ? ya >> 5 : w0, v1 = ((yl + 31u) >> 5) < w0 + nw ? (yl + 31u) >> 5 : w0 + nw;
+                                for (uint32_t v = v0; v < v1; ++v) ptx_atomic_or(&cw[v - w0], ptx_span_mask(ya, yl, v));
                             }
-                            ptx_patch_put(dst, open, o++, t, add ? PTX_PATCH_ADDMARK : PTX_PATCH_REMOVEMARK, PTX_VIS_AT((w << 5) + b), PTX_VIS_AT(nxt));
+                        }
+                        PTX_SYNC_T();
+                    }
+                    PTX_FOR(wi, nw) {
+                        const uint32_t w = w0 + wi;
+                        const uint32_t m = S.ld(&S.defined[w]) & PTX_RANGE_MASK(w);
+                        const uint32_t upd = fast ? m : m & ~cw[wi];
+                        const uint32_t old = S.ld(&S.mb[w].on[li]);
+                        if (upd) S.st(&S.mb[w].on[li], add ? old | upd : old & ~upd);
+                        if (per_slot) {
+                            cw[wi] = upd & ~old; /* (the two together: the slots the op wins) */
+                            cnt[wi] = upd & old;
+                        } else {
+                            const uint32_t ch = upd & (add ? ~old : old);
+                            PTX_FINISH_WORD(wi, w, m, ch);
+                        }
+                    }
+                    if (per_slot) {
+                        S.before_read();
+                        PTX_SYNC_T();
+                        const uint32_t my_url = my_id & PTX_ATTR_ID_MASK;
+                        PTX_FOR(j, nw << 5) {
+                            const uint32_t wi = j >> 5, bit = j & 31u;
+                            const bool both = (cnt[wi] >> bit) & 1u; /* the link was on: changed iff the urls differ */
+                            if (both || ((cw[wi] >> bit) & 1u)) { /* (a lane only ever sets ITS bit of cw, and only where `both`: the test reads what the pass before wrote) */
+                                const uint32_t s = ((w0 + wi) << 5) + bit;
+                                if (both && (S.ldw(&S.lurl[s]) & PTX_ATTR_ID_MASK) != my_url) ptx_atomic_or(&cw[wi], 1u << bit);
+                                S.stw(&S.lurl[s], my_id);
+                            }
+                        }
+                        PTX_SYNC_T();
+                        PTX_FOR(wi, nw) {
+                            const uint32_t w = w0 + wi;
+                            const uint32_t m = S.ld(&S.defined[w]) & PTX_RANGE_MASK(w);
+                            const uint32_t ch = cw[wi];
+                            PTX_FINISH_WORD(wi, w, m, ch);
+                        }
+                    }
+                } else {
+                    /* comments: the last-applied covering op with this id decides (this op is not registered yet): per word, the id's chain latest first */
+                    PTX_FOR(wi, nw) {
+                        const uint32_t w = w0 + wi;
+                        const uint32_t m = S.ld(&S.defined[w]) & PTX_RANGE_MASK(w);
+                        uint32_t und = m, onm = 0;
+                        for (uint32_t y = y0; y != PTX_CHAIN_NONE && und; y = S.ld(&S.cprev[y])) {
+                            const uint32_t c = ptx_span_mask(S.ld(&S.ca[y]), S.ld(&S.cb[y]), w) & und;
+                            if ((S.ld(&S.cadd[y >> 5]) >> (y & 31u)) & 1u) onm |= c;
+                            und &= ~c;
+                        }
+                        const uint32_t any = S.ld(&S.mb[w].ac);
+                        const uint32_t ch = add ? m & ~onm : m & (onm | ~any); /* remove on no comment key: undefined -> [] */
+                        if (m) S.st(&S.mb[w].ac, any | m);
+                        PTX_FINISH_WORD(wi, w, m, ch);
+                    }
+                }
+                PTX_SYNC_T();
+                const uint32_t P = ptx_scan_excl<uint32_t, 1, kThreads>(cnt, nw, H->scan_tmp);
+                if (P) {
+                    PTX_FOR(wi, nw) {
+                        uint32_t R = cw[wi];
+                        if (R) {
+                            const uint32_t w = w0 + wi;
+                            const uint32_t m = S.ld(&S.defined[w]) & PTX_RANGE_MASK(w);
+                            uint32_t o = prun + cnt[wi];
+                            while (R) {
+                                const uint32_t b = (uint32_t)__builtin_ctz(R);
+                                R &= R - 1u;
+                                const uint32_t above = m & ptx_bits_from(b + 1u);
+                                const uint32_t nxt = above ? (w << 5) + (uint32_t)__builtin_ctz(above) : S.next_defined(w, slot_a, lim, whi);
+                                ptx_patch_put(dst, open, o++, t, add ? PTX_PATCH_ADDMARK : PTX_PATCH_REMOVEMARK, PTX_VIS_AT((w << 5) + b), PTX_VIS_AT(nxt));
+                            }
                         }
                     }
                 }
-            }
-            npatch = p0 + P;
-            if (ty == PTX_MARK_COMMENT && my_id < Kid && ncom < Kc) {
+                prun += P;
+                tw += Store::kTile;
+                if (Store::kTile) PTX_SYNC_T(); /* the tile buffers are rewritten next */
+            } while (Store::kTile && tw < nw_all);
+            npatch = prun;
+            if (lww) { /* the op joins the table of its type */
+                if (toff[li] + ntab[li] <= Kl) { /* (always, with the census' header: the table has Kl + 1 entries) */
+                    PTX_LEADER {
+                        if (kWide) {
+                            S.stw(&S.tab[2u * (toff[li] + ntab[li])], (uint64_t)t | ((uint64_t)slot_a << 32));
+                            S.stw(&S.tab[2u * (toff[li] + ntab[li]) + 1u], (uint64_t)lim);
+                        } else {
+                            S.stw(&S.tab[toff[li] + ntab[li]], (uint64_t)t | ((uint64_t)slot_a << 16) | ((uint64_t)lim << 32));
+                        }
+                    }
+                    ntab[li] += 1u;
+                }
+                if (fast) maxop[li] = my_op;
+            } else if (my_id < Kid && ncom < Kc) {
                 PTX_LEADER {
-                    ca[ncom] = (slot_t)slot_a;
-                    cb[ncom] = (slot_t)slot_b;
-                    PTX_G_ST16(&ccid[ncom], my_id);
-                    if (add) cadd[ncom >> 5] |= 1u << (ncom & 31u);
-                    cprev[ncom] = (uint16_t)y0;
-                    PTX_G_ST16(&ctail[my_id], ncom);
+                    S.st(&S.ca[ncom], (slot_t)slot_a);
+                    S.st(&S.cb[ncom], (slot_t)slot_b);
+                    S.stw(&S.ccid[ncom], (uint16_t)my_id);
+                    if (add) S.st(&S.cadd[ncom >> 5], S.ld(&S.cadd[ncom >> 5]) | (1u << (ncom & 31u)));
+                    S.st(&S.cprev[ncom], (uint16_t)y0);
+                    S.stw(&S.ctail[my_id], (uint16_t)ncom);
                 }
                 ncom += 1u;
             }
             PTX_SYNC_T();
 #undef PTX_FINISH_WORD
-#undef PTX_NEXT_AFTER_WORD
 #undef PTX_RANGE_MASK
         }
     }
     PTX_SYNC_T(); /* the chunk buffers are rewritten next */
     }
 #undef PTX_DEFINE_SLOT
-#undef PTX_RESERVE
 #undef PTX_VIS_AT
-#undef PTX_G_LD16
-#undef PTX_G_ST16
-#undef PTX_G_LD32
-#undef PTX_G_LD64
-#undef PTX_G_ST64
-#undef PTX_G_ST32
-#undef PTX_G_FENCE
-    PTX_LEADER {
-        ptx_patch_log pl;
-        const uint32_t produced = first < N ? npatch : 0u; /* (first >= N: nothing was asked for) */
-        pl.status = produced > room ? (uint32_t)PTX_ERR_CAPACITY : (uint32_t)PTX_OK;
-        pl.n_patches = produced;
-        A.plogs[log] = pl;
-        if (A.ext_off) {
-            A.ext_off[3 * (uint64_t)log] = H->ext_cap[0] ? ((uint64_t)H->ext_hi[0] << 32) | H->ext_lo[0] : ~0ull;
-            A.ext_off[3 * (uint64_t)log + 1] = H->ext_cap[1] ? ((uint64_t)H->ext_hi[1] << 32) | H->ext_lo[1] : ~0ull;
-            A.ext_off[3 * (uint64_t)log + 2] = H->ext_cap[0];
-        }
-    }
+    PTX_LEADER { ptx_replay_finish(A, log, H, first < N ? npatch : 0u /* (first >= N: nothing was asked for) */, room); }
+}
+
+/* the three LDS builds: ptx_replay_kernel, _gwin and _wide */
+template <uint32_t kThreads, bool kGWin = false, bool kWide = false>
+PTX_DEV void ptx_replay_log(const PtxReplayArgs& A, uint32_t log, uint8_t* lds) {
+    PtxReplayLdsStore<kGWin, kWide> S;
+    S.win = kGWin ? A.win_scratch + A.win_off[log] : nullptr;
+    ptx_replay_walk<kThreads>(A, log, lds, A.lds_bytes, S);
 }
