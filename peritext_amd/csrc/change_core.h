@@ -21,6 +21,12 @@
  * One 64-thread workgroup (one wave) per replica log, the element list in document order in LDS (one u32 per element:
  * dense element index | tombstone | after-defined), sequential over the InputOperations — the list primitives are the
  * 64-wide ballots of gen_core.h.  Compiled two ways like merge_core.h (hipcc: the product; g++ -DPTX_EMU: CPU tests).
+ *
+ * Evidence: the reference's own 125 change() calls (tests/change_script.py) and, at the edges of the three list primitives — select across 64-lane
+ * chunks, lookAfterTombstones across chunks anchored at pos + 1, the 16-byte-block gap opener across its 64-block steps — the probe tables of
+ * tests/change_probe.py (tests/test_emu_change_edges.py; tests/test_gpu_change_edges.py, also with every list in global scratch): every Change against
+ * the oracle's, with read-outs of the list inside the call.  The emulation replaces the ballots and the gap opener by plain loops, so the GPU file is
+ * the only check of ptx_list_shift_up's device build.
  */
 #pragma once
 #include "gen_core.h"

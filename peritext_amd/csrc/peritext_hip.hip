@@ -2610,6 +2610,8 @@ ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* m
     }
     uint64_t need = 4096;
     /* round 6: the element list of a log that does not fit one CU's LDS (more than ~40 000 elements) lives in a slice of global scratch */
+    /* (tests: PTX_CHANGE_LIST_IN_HBM=1 puts the list of EVERY log there, so that documents of a few dozen elements run the form) */
+    const bool all_in_hbm = getenv("PTX_CHANGE_LIST_IN_HBM") != nullptr;
     std::vector<uint64_t> list_off((size_t)L + 1, 0);
     for (uint32_t l = 0; l < L; ++l) {
         list_off[l + 1] = list_off[l];
@@ -2617,7 +2619,7 @@ ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* m
             const bool rows = log_off[l + 1] > log_off[l];
             const uint64_t ks = rows ? ((uint64_t)hdr[l].max_counter + 1) * ((uint64_t)std::min<uint32_t>(hdr[l].max_actor, 4095u) + 1) : 1;
             const uint64_t n_l = rows ? hdr[l].n_ins : 0;
-            const bool in_hbm = ptx_change_lds_need(n_l, grow[l], ks, na) > ctx->max_lds;
+            const bool in_hbm = all_in_hbm || ptx_change_lds_need(n_l, grow[l], ks, na) > ctx->max_lds;
             if (in_hbm) list_off[l + 1] += ptx_change_list_words(n_l, grow[l]);
             need = std::max<uint64_t>(need, ptx_change_lds_need(n_l, grow[l], ks, na, in_hbm));
         }
