@@ -113,6 +113,8 @@ enum {
     PTX_ERR_CAPACITY = 5,        /* log beyond what this build holds (ptx_merge: beyond the HBM-staged path's bounds or a forced LDS window; the on-chip-only entry points: beyond one CU's LDS) */
     PTX_ERR_BAD_OP = 6,          /* malformed row: unknown action / mark type / comment id beyond the header's n_comment_ids */
     PTX_ERR_INDEX_OOB = 7,       /* RangeError "List index out of bounds"    micromerge.ts:804 (ptx_change only) */
+    /* per-pair (ptx_sync_replicas only) */
+    PTX_ERR_SYNC_NOT_CONVERGED = 8, /* "applyChanges did not converge"       test/merge.ts:18-19: more attempts than max_attempts, or a pass that admits nothing */
     /* call-level */
     PTX_ERR_INVALID_ARG = 100,
     PTX_ERR_HIP = 101,           /* a HIP runtime call failed; see ptx_last_error */
@@ -522,6 +524,29 @@ typedef struct ptx_input_ops {
 ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* merged, const ptx_input_ops* in, ptx_dbatch** made, uint32_t* status_out);
 /* Streaming append with `more` already resident (e.g. the output of ptx_change): log l of *out = log l of `base` + log l of `more`. */
 ptx_status ptx_batch_append_device(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dbatch* more, ptx_dbatch** out);
+
+/* ---- sync of replica logs: getMissingChanges + applyChanges (test/merge.ts:4-38; test/fuzz.ts:181-199 calls them in both directions after every
+ * edit) for MANY (source, target) pairs at once, the logs staying resident ----
+ * Pair p = (src_log[p], dst_log[p]) (HOST arrays), two replicas of the same document (they share the actor ranks).  Per pair, pinned to the reference:
+ *   clocks        clock[a] = the largest seq of actor a in a log, 0 = absent (exact lo | hi << 16 with chg_env_hi)
+ *   missing bag   the actors in the order of their FIRST APPEARANCE in the source log (the key order of source.clock, merge.ts:29); per actor the source's
+ *                 changes with seq > the target's clock[a], in log order; an actor the target never saw contributes all of them (merge.ts:30-32)
+ *   retry order   the queue of merge.ts:7-20: take the head, admit it as applyChange does (micromerge.ts:499-511: seq == clock[actor] + 1 and clock[b] >=
+ *                 deps[b] for every non-zero dep, the own actor's included), push it to the back on failure
+ *   the guard     merge.ts:18 throws once the 10 002nd attempt has been made, also when that attempt emptied the queue: a pair that takes more than
+ *                 max_attempts attempts (10 001 = the reference; 0 = unbounded) is PTX_ERR_SYNC_NOT_CONVERGED, and so is — whatever max_attempts — a pass
+ *                 that admits nothing (a source log no replica could have applied: the reference spins into its guard, this call terminates)
+ * *more = a resident batch of base's n_logs logs, envelope (the wide column iff `base` has one), max_actors and computed headers: log dst_log[p] holds the
+ * admitted changes of pair p IN ADMITTED ORDER with their op rows, every other log is empty — made for ptx_batch_append_device(base, more).  All pairs read
+ * `base` as it is: a bidirectional sync is the two pairs (l, r) and (r, l) of one call (what r received from l is never missing for l: fuzz.ts:198-199).  A log
+ * may be a source any number of times and a source and a target at once; a log that is a target twice is PTX_ERR_INVALID_ARG; src == dst is an empty log.
+ * status_out[p] (caller memory): PTX_OK, PTX_ERR_SYNC_NOT_CONVERGED, PTX_ERR_CAPACITY (a narrow envelope with a saturated value, 65 535, in either log) or
+ * PTX_ERR_BAD_OP (an actor rank >= max_actors); a failed pair contributes an EMPTY log and `base` is never touched (the reference leaves the target
+ * half-updated — not reproduced).  merge.ts:15 catches every error, op-level ones too; this call looks at the ENVELOPE only: a change whose ops would throw is
+ * ordered like any other and the grown log reports its op-level status at its merge.  A batch without the envelope is PTX_ERR_INVALID_ARG.  No bound on the
+ * logs below the batch format's own; the per-actor tables (24 bytes per actor) must fit one CU's LDS.  The call synchronises. */
+ptx_status ptx_sync_replicas(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_pairs, const uint32_t* src_log, const uint32_t* dst_log, uint32_t max_attempts,
+                             ptx_dbatch** more, uint32_t* status_out);
 
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {

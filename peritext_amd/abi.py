@@ -42,6 +42,7 @@ ERR_DUPLICATE_OP = 4
 ERR_CAPACITY = 5
 ERR_BAD_OP = 6
 ERR_INDEX_OOB = 7
+ERR_SYNC_NOT_CONVERGED = 8  # per pair (ptx_sync_replicas): "applyChanges did not converge", reference/test/merge.ts:18-19
 ERR_INVALID_ARG = 100
 ERR_HIP = 101
 ERR_NO_DEVICE = 102
@@ -56,6 +57,7 @@ STATUS_NAMES = {
     5: "log exceeds on-chip capacity",
     6: "malformed op row",
     7: "RangeError: List index out of bounds",
+    8: "applyChanges did not converge",
 }
 
 
@@ -323,6 +325,7 @@ FUNCTIONS = {
     "ptx_resolve_cursors": (C.c_int32, [vp, vp, vp, C.c_uint32, u32p, u8p, u64p, u64p, u32p]),
     "ptx_change": (C.c_int32, [vp, vp, vp, C.POINTER(ptx_input_ops), C.POINTER(vp), u32p]),
     "ptx_batch_append_device": (C.c_int32, [vp, vp, vp, C.POINTER(vp)]),
+    "ptx_sync_replicas": (C.c_int32, [vp, vp, C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(vp), u32p]),
     "ptx_batch_download": (C.c_int32, [vp, vp, C.POINTER(ptx_host_batch)]),
     "ptx_host_batch_free": (None, [C.POINTER(ptx_host_batch)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),

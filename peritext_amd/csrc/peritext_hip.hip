@@ -33,6 +33,7 @@
 #include "change_core.h"
 #include "cursor_core.h"
 #include "rootmap_core.h"
+#include "sync_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -187,6 +188,16 @@ extern "C" __global__ void __launch_bounds__(64) ptx_gen_kernel_r8(PtxGenArgs A)
 extern "C" __global__ void __launch_bounds__(64) ptx_change_kernel(PtxChangeArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
     if (blockIdx.x < A.n_logs) ptx_change_log<64>(A, blockIdx.x, ptx_lds);
+}
+
+/* the sync between two replicas (sync_core.h): one wave per pair plans (missing changes in retry order), one workgroup per pair gathers their rows */
+#define PTX_SYNC_GATHER_THREADS 256
+extern "C" __global__ void __launch_bounds__(64) ptx_sync_plan_kernel(PtxSyncArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
+    if (blockIdx.x < A.n_pairs) ptx_sync_plan_pair<64>(A, blockIdx.x, ptx_lds);
+}
+extern "C" __global__ void __launch_bounds__(PTX_SYNC_GATHER_THREADS) ptx_sync_gather_kernel(PtxSyncArgs A, PtxSyncGatherArgs G) {
+    if (blockIdx.x < A.n_pairs) ptx_sync_gather_pair<PTX_SYNC_GATHER_THREADS>(A, G, blockIdx.x);
 }
 
 /* the map objects of a replica (rootmap_core.h): one wave per replica log; a first kernel counts the map rows (capacity of the entry rows) */
@@ -938,7 +949,7 @@ ptx_status ptx_create(int device_ordinal, uint32_t flags, ptx_ctx** out) {
     ctx->own_stream = ctx->stream;
     /* one workgroup may use the CU's whole 160 KiB of LDS */
     {
-        const void* kernels[] = {(const void*)ptx_merge_kernel, (const void*)ptx_merge_kernel_rest, (const void*)ptx_merge_kernel_many, (const void*)ptx_merge_kernel_many_wide, (const void*)ptx_merge_kernel_diag, (const void*)ptx_merge_kernel_w7, (const void*)ptx_merge_kernel_rest_w7, (const void*)ptx_merge_kernel_lean64, (const void*)ptx_merge_kernel_lean128, (const void*)ptx_merge_kernel_lean192, (const void*)ptx_merge_kernel_lean256, (const void*)ptx_replay_kernel, (const void*)ptx_replay_kernel_gwin, (const void*)ptx_replay_kernel_wide, (const void*)ptx_gen_kernel, (const void*)ptx_gen_kernel_r8, (const void*)ptx_change_kernel, (const void*)ptx_cursor_kernel, (const void*)ptx_rootmap_kernel};
+        const void* kernels[] = {(const void*)ptx_merge_kernel, (const void*)ptx_merge_kernel_rest, (const void*)ptx_merge_kernel_many, (const void*)ptx_merge_kernel_many_wide, (const void*)ptx_merge_kernel_diag, (const void*)ptx_merge_kernel_w7, (const void*)ptx_merge_kernel_rest_w7, (const void*)ptx_merge_kernel_lean64, (const void*)ptx_merge_kernel_lean128, (const void*)ptx_merge_kernel_lean192, (const void*)ptx_merge_kernel_lean256, (const void*)ptx_replay_kernel, (const void*)ptx_replay_kernel_gwin, (const void*)ptx_replay_kernel_wide, (const void*)ptx_gen_kernel, (const void*)ptx_gen_kernel_r8, (const void*)ptx_change_kernel, (const void*)ptx_cursor_kernel, (const void*)ptx_rootmap_kernel, (const void*)ptx_sync_plan_kernel};
         e = hipSuccess;
         for (const void* k : kernels)
             if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds);
@@ -2838,6 +2849,154 @@ ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* m
         return st;
     }
     *made = b;
+    return PTX_OK;
+}
+
+/* ---- sync of replica logs: the missing changes of every (source, target) pair in retry order (sync_core.h) ---- */
+ptx_status ptx_sync_replicas(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_pairs, const uint32_t* src_log, const uint32_t* dst_log, uint32_t max_attempts, ptx_dbatch** more,
+                             uint32_t* status_out) {
+    if (!ctx || !base || !more || (n_pairs && (!src_log || !dst_log || !status_out))) return PTX_ERR_INVALID_ARG;
+    *more = nullptr;
+    const uint32_t L = base->n_logs, P = n_pairs, na = base->max_actors;
+    if (!base->chg_off || !base->chg_hdr || !base->chg_env || na == 0) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_sync_replicas needs the Change envelope of the batch (the replicas' clocks)");
+    {
+        std::vector<uint8_t> is_target(std::max<uint32_t>(L, 1), 0);
+        const int bad = ptx_sync_check_pairs(L, P, src_log, dst_log, is_target.data());
+        if (bad == 1) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_sync_replicas: a pair names a log the batch does not have");
+        if (bad == 2) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_sync_replicas: a log is the target of two pairs (a target log takes one source per call)");
+    }
+    const uint64_t lds_need = (ptx_sync_lds_need(na) + 255) & ~255ull;
+    if (lds_need > ctx->max_lds) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_sync_replicas: the per-actor tables of max_actors do not fit one CU's LDS");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    /* the pinned staging block of the context's small uploads, grown on demand */
+    auto staging = [&](size_t bytes) -> hipError_t {
+        if (ctx->up_h_cap >= bytes) return hipSuccess;
+        if (ctx->up_h) (void)hipHostFree(ctx->up_h);
+        ctx->up_h = nullptr;
+        ctx->up_h_cap = 0;
+        hipError_t e = hipHostMalloc((void**)&ctx->up_h, 2 * bytes, hipHostMallocDefault);
+        if (e == hipSuccess) ctx->up_h_cap = 2 * bytes;
+        return e;
+    };
+    uint8_t *d_in = nullptr, *d_off = nullptr;
+    uint32_t *d_scratch = nullptr, *d_out = nullptr;
+    ptx_dbatch* b = nullptr;
+    auto drop = [&]() {
+        (void)ptx_dev_free(d_in);
+        (void)ptx_dev_free(d_off);
+        (void)ptx_dev_free(d_scratch);
+        (void)ptx_dev_free(d_out);
+        d_in = d_off = nullptr;
+        d_scratch = d_out = nullptr;
+    };
+#define PTX_TRYS(call)                                  \
+    do {                                                \
+        hipError_t _e = (call);                         \
+        if (_e != hipSuccess) {                         \
+            std::string msg = std::string(#call) + ": " + hipGetErrorString(_e); \
+            drop();                                     \
+            ptx_batch_free(ctx, b);                     \
+            return fail(ctx, _e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, msg); \
+        }                                               \
+    } while (0)
+    /* the envelope offsets of the base size the scratch slices: one small copy through the pinned block */
+    const size_t off_bytes = ((size_t)L + 1) * 8, pair_bytes = ((size_t)P * 4 + 15) & ~(size_t)15, scr_bytes = ((size_t)P + 1) * 8;
+    const size_t in_bytes = 2 * pair_bytes + scr_bytes;
+    PTX_TRYS(staging(std::max(std::max(off_bytes, in_bytes), 2 * off_bytes)));
+    PTX_TRYS(hipMemcpyAsync(ctx->up_h, base->chg_off, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PTX_TRYS(hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> coff((size_t)L + 1), scr((size_t)P + 1, 0);
+    memcpy(coff.data(), ctx->up_h, off_bytes);
+    for (uint32_t p = 0; p < P; ++p) scr[p + 1] = scr[p] + ptx_sync_scratch_words(coff[src_log[p] + 1] - coff[src_log[p]]);
+    std::vector<uint32_t> outw(3 * (size_t)P + 1, 0);
+    if (P) {
+        PTX_TRYS(ptx_dev_malloc((void**)&d_in, in_bytes));
+        PTX_TRYS(dalloc(&d_scratch, scr[P]));
+        PTX_TRYS(dalloc(&d_out, 3 * (uint64_t)P));
+        memcpy(ctx->up_h, src_log, (size_t)P * 4);
+        memcpy(ctx->up_h + pair_bytes, dst_log, (size_t)P * 4);
+        memcpy(ctx->up_h + 2 * pair_bytes, scr.data(), scr_bytes);
+        PTX_TRYS(hipMemcpyAsync(d_in, ctx->up_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PtxSyncArgs A;
+    memset(&A, 0, sizeof(A));
+    A.log_off = base->log_off;
+    A.chg_off = base->chg_off;
+    A.chg_hdr = base->chg_hdr;
+    A.chg_env = base->chg_env;
+    A.chg_env_hi = base->chg_env_hi;
+    A.max_actors = na;
+    A.n_pairs = P;
+    A.max_attempts = max_attempts;
+    A.src_log = (const uint32_t*)d_in;
+    A.dst_log = (const uint32_t*)(d_in + pair_bytes);
+    A.scr_off = (const uint64_t*)(d_in + 2 * pair_bytes);
+    A.scratch = d_scratch;
+    A.status = d_out;
+    A.n_admitted = d_out + P;
+    A.n_rows = d_out + 2 * (size_t)P;
+    A.lds_bytes = (uint32_t)lds_need;
+    if (P) {
+        hipLaunchKernelGGL(ptx_sync_plan_kernel, dim3(P), dim3(64), (uint32_t)lds_need, ctx->stream, A);
+        PTX_TRYS(hipGetLastError());
+        /* one copy back: status, admitted changes and rows of every pair */
+        PTX_TRYS(staging(3 * (size_t)P * 4));
+        PTX_TRYS(hipMemcpyAsync(ctx->up_h, d_out, 3 * (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYS(hipStreamSynchronize(ctx->stream));
+        memcpy(outw.data(), ctx->up_h, 3 * (size_t)P * 4);
+        memcpy(status_out, outw.data(), (size_t)P * 4);
+    }
+    /* `more`: log dst_log[p] = the admitted changes of pair p, every other log empty */
+    std::vector<uint64_t> doff((size_t)L + 1, 0), dcoff((size_t)L + 1, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+        dcoff[(size_t)dst_log[p] + 1] = outw[(size_t)P + p];
+        doff[(size_t)dst_log[p] + 1] = outw[2 * (size_t)P + p];
+    }
+    for (uint32_t l = 0; l < L; ++l) {
+        doff[l + 1] += doff[l];
+        dcoff[l + 1] += dcoff[l];
+    }
+    b = new ptx_dbatch();
+    b->n_logs = L;
+    b->n_ops = doff[L];
+    b->max_actors = na;
+    b->n_changes = dcoff[L];
+    const uint64_t ES = PTX_ENV_STRIDE(na);
+    PTX_TRYS(dalloc(&b->log_off, (uint64_t)L + 1));
+    PTX_TRYS(dalloc(&b->chg_off, (uint64_t)L + 1));
+    PTX_TRYS(staging(2 * off_bytes));
+    memcpy(ctx->up_h, doff.data(), off_bytes);
+    memcpy(ctx->up_h + off_bytes, dcoff.data(), off_bytes);
+    PTX_TRYS(hipMemcpyAsync(b->log_off, ctx->up_h, off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PTX_TRYS(hipMemcpyAsync(b->chg_off, ctx->up_h + off_bytes, off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PTX_TRYS(dalloc(&b->op_id, b->n_ops));
+    PTX_TRYS(dalloc(&b->ref_a, b->n_ops));
+    PTX_TRYS(dalloc(&b->ref_b, b->n_ops));
+    PTX_TRYS(dalloc(&b->payload, b->n_ops));
+    PTX_TRYS(dalloc(&b->action, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYS(dalloc(&b->mark_type, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYS(dalloc(&b->side_a, b->n_ops));
+    PTX_TRYS(dalloc(&b->side_b, b->n_ops));
+    PTX_TRYS(dalloc(&b->log_hdr, (uint64_t)L));
+    PTX_TRYS(dalloc(&b->chg_hdr, b->n_changes + PTX_ENV_PAD));
+    PTX_TRYS(dalloc(&b->chg_env, (b->n_changes + PTX_ENV_PAD) * ES));
+    if (base->chg_env_hi) PTX_TRYS(dalloc(&b->chg_env_hi, (b->n_changes + PTX_ENV_PAD) * ES));
+    if (P && b->n_changes) {
+        PtxSyncGatherArgs G = {base->op_id, base->ref_a, base->ref_b, base->payload, base->action, base->mark_type, base->side_a, base->side_b,
+                               b->op_id, b->ref_a, b->ref_b, b->payload, b->action, b->mark_type, b->side_a, b->side_b,
+                               b->chg_hdr, b->chg_env, b->chg_env_hi, b->log_off, b->chg_off};
+        hipLaunchKernelGGL(ptx_sync_gather_kernel, dim3(P), dim3(PTX_SYNC_GATHER_THREADS), 0, ctx->stream, A, G);
+        PTX_TRYS(hipGetLastError());
+    }
+    PTX_TRYS(hipStreamSynchronize(ctx->stream));
+#undef PTX_TRYS
+    drop();
+    const ptx_status st = census_and_shape(ctx, b, false);
+    if (st != PTX_OK) {
+        ptx_batch_free(ctx, b);
+        return st;
+    }
+    *more = b;
     return PTX_OK;
 }
 

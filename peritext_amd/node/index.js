@@ -34,6 +34,7 @@ const STATUS_MESSAGES = {
     5: "log exceeds on-chip capacity",
     6: "malformed op row",
     7: "List index out of bounds" /* :804 */,
+    8: "applyChanges did not converge" /* test/merge.ts:18-19 (syncMany only) */,
 }
 const IN = { INSERT: 0, DELETE: 1, ADDMARK: 2, REMOVEMARK: 3, MAKELIST: 4, MAPSET: 5, MAPDEL: 6 }
 const IN_OBJ_NEW = 0x80000000 /* ptx_input_ops.index of a map op: the object made by row k of this log's output */ /* ptx_input_ops.action */
@@ -877,6 +878,32 @@ class MergeEngine {
             })
         })
         return { changes, status }
+    }
+    /**
+     * getMissingChanges + applyChanges (reference/test/merge.ts:4-38) for many replica pairs in ONE call (ptx_sync_replicas): docs = the replica logs
+     * applied so far (Change[][][]), pairs = [{doc, from, to}] replica indices of one document; a bidirectional sync is {from: l, to: r} and {from: r, to: l}
+     * (both read the logs as they are); a replica may be the `to` of one pair only.  opts.maxAttempts: the reference's guard (default 10001; 0 = unbounded).
+     * Returns {changes: Change[][] (per pair: what `to` lacks, in the order it admits it), status: number[]} — a pair whose status is not 0 contributes
+     * nothing (STATUS_MESSAGES: 8 = the reference's "applyChanges did not converge").
+     */
+    syncMany(docs, pairs, opts) {
+        const batch = encodeDocs(docs)
+        const first = []
+        let n = 0
+        docs.forEach(logs => {
+            first.push(n)
+            n += logs.length
+        })
+        const src = Uint32Array.from(pairs, p => first[p.doc] + p.from), dst = Uint32Array.from(pairs, p => first[p.doc] + p.to)
+        const maxAttempts = opts && opts.maxAttempts !== undefined ? opts.maxAttempts : 10001
+        const raw = this.addon.syncReplicas(this.ctx, batch, { src, dst, maxAttempts })
+        const more = Object.assign(raw.batch, { values: batch.values, urls: batch.urls, logDoc: batch.logDoc, docActors: batch.docActors, docComments: batch.docComments, keys: batch.keys, mapValues: batch.mapValues })
+        const changes = pairs.map((p, k) => {
+            let textObj = null
+            for (const log of docs[p.doc]) for (const ch of log) for (const op of ch.ops) if (op.action === "makeList" && textObj === null) textObj = op.opId
+            return decodeChanges(more, dst[k], textObj)
+        })
+        return { changes, status: Array.from(raw.status) }
     }
     /**
      * A replica handle with the reference's per-replica calls; all handles of one engine are merged in ONE launch.
