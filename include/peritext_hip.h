@@ -277,6 +277,8 @@ typedef struct ptx_dresult ptx_dresult;  /* result buffers resident in HBM */
                                       tables of applied ops then live in global memory: four times the logs per CU); tuning / A-B */
 #define PTX_FLAG_REPLAY_HBM_STATE 16u /* ptx_replay_patches replays EVERY log with its state in global scratch (by default only the logs whose state does not fit one
                                          CU's LDS: that kernel pays a trip to the L2 per state access); tests / measurement */
+#define PTX_FLAG_ACCUM_HBM_STATE 32u /* ptx_accumulate_patches / ptx_check_patches accumulate EVERY log with its state in global scratch (by default only the logs whose
+                                        state does not fit one CU's LDS); tests / measurement */
 #define PTX_FLAG_PAD_GATHER 4u   /* ptx_allgather_digests always takes its padded path (pack, all-gather of max(counts) pairs per rank, compact on the
                                     device) even when every rank holds the same number of logs: same result; lets a one-GPU host exercise that path */
 
@@ -402,6 +404,41 @@ ptx_status ptx_replay_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresu
  * in the log.  first_row[l] >= the log's rows: an empty stream. */
 ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const uint32_t* first_row, ptx_patches* out);
 void ptx_patches_free(ptx_patches* p);
+
+/* ---- the consumer side: accumulatePatches (reference/test/accumulatePatches.ts; the fuzzer's third assertion, test/fuzz.ts:245-278) ----
+ * A stream is applied record by record to a list of characters {value id, attr word, set of comment ids} that starts empty:
+ *   PTX_PATCH_MAKELIST        nothing
+ *   PTX_PATCH_INSERT          a character with value payload[row], attr b and no ids at index a; it is "the last inserted character"
+ *   PTX_PATCH_INSERT_COMMENT  id a joins the last inserted character's set (legal only right behind an INSERT or another INSERT_COMMENT)
+ *   PTX_PATCH_DELETE          b characters from index a go (a foreign stream may fold deletes: b > 1)
+ *   PTX_PATCH_ADDMARK / PTX_PATCH_REMOVEMARK  characters [a, b), the type = mark_type[row]: strong / em set / clear the flag; link sets PTX_ATTR_LINK and
+ *                             payload[row] / clears both; comment sets PTX_ATTR_COMMENT and adds id payload[row] / sets PTX_ATTR_COMMENT (the key stays, possibly
+ *                             []) and discards THAT id only (the reference's checker drops the whole key; the replica itself does not, peritext.ts:318-320)
+ * The result is the canonical form of the merge: values, a span wherever attr or the id set changes, one comment interval per id and maximal run, n_elems = the
+ * INSERT records, and the digest the merge computes for those rows.  Per-log status: the stream's own when that is not PTX_OK (no rows, digest {0, 0});
+ * PTX_ERR_INDEX_OOB (an insert index beyond the length, a delete that reaches past the end, a mark with b > length or a > b; a == b is an empty range);
+ * PTX_ERR_BAD_OP (an unknown kind, row >= the log's rows, an INSERT_COMMENT behind anything else, a comment id >= the log header's n_comment_ids, a mark
+ * record whose row is not a mark op); PTX_ERR_CAPACITY (more INSERT records than the log has insert rows, or more output rows than the log has rows).  A failed
+ * log has no rows, reserved[1] = the index of its first bad record (0xffffffff otherwise); the other logs of the call are unaffected. */
+/* host records of any origin (p->patch_off / logs / patches; p->n_logs == the batch's logs) -> canonical rows (elem_rank NULL); synchronises */
+ptx_status ptx_accumulate_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_patches* p, ptx_result* out);
+
+typedef struct ptx_patch_check_log {
+    uint32_t status;            /* as above */
+    uint32_t agrees;            /* the stream's {n_elems, n_visible, n_spans, n_cintervals, digest} equal the merge's */
+    uint32_t n_patches;         /* records of the log's stream */
+    uint32_t first_bad_record;  /* 0xffffffff when status == PTX_OK */
+    uint64_t digest[2];         /* of the accumulated stream */
+} ptx_patch_check_log;
+/* Replay every log of `b` (whole streams, as ptx_replay_patches) and accumulate the records ON THE DEVICE, where the replay wrote them: no record is downloaded.
+ * `r` = ptx_merge of `b` WITH elem_rank, complete.  out: host [n_logs]; *n_disagree = the logs with status PTX_OK and agrees == 0.  Synchronises. */
+ptx_status ptx_check_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, ptx_patch_check_log* out, uint64_t* n_disagree);
+/* Diagnostic: HIP-event durations of the last successful ptx_check_patches of the context (both 0 before the first).
+ *   *replay_ms  the replay launches of the LAST replay attempt only (ptx_patches.kernel_ms): where the replay ran twice, because the record arena or a log's extent
+ *               ran out, the first attempt's kernel time is not in it.
+ *   *accum_ms   the accumulate launches, a SUM over the packed ranges (one range unless device memory is short or PTX_REPLAY_PACK_RECORDS is set); the
+ *               pack kernel's time is in neither figure. */
+ptx_status ptx_check_patches_ms(const ptx_ctx* ctx, float* replay_ms, float* accum_ms);
 
 /* ---- the map objects of a replica: getRoot() (micromerge.ts:443-449) ----
  * applyOp on a map object (micromerge.ts:572-602) keeps, per key, the op with the largest opId (compareOpIds): last writer wins;

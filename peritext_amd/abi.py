@@ -32,6 +32,7 @@ FLAG_NO_ADMISSION = 2
 FLAG_PAD_GATHER = 4
 FLAG_REPLAY_LDS_ONLY = 8
 FLAG_REPLAY_HBM_STATE = 16  # ptx_replay_patches: every log through the HBM-state kernel (a test and measurement knob)
+FLAG_ACCUM_HBM_STATE = 32  # ptx_accumulate_patches / ptx_check_patches: every log with its state in global scratch (a test and measurement knob)
 COMM_ID_BYTES = 128
 
 PTX_OK = 0
@@ -169,6 +170,10 @@ class ptx_patch_log(C.Structure):
     _fields_ = [("status", C.c_uint32), ("n_patches", C.c_uint32)]
 
 
+class ptx_patch_check_log(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("agrees", C.c_uint32), ("n_patches", C.c_uint32), ("first_bad_record", C.c_uint32), ("digest", C.c_uint64 * 2)]
+
+
 class ptx_root_entry(C.Structure):
     _fields_ = [("obj", C.c_uint64), ("key", C.c_uint32), ("row", C.c_uint32), ("kind", C.c_uint32), ("value", C.c_uint32)]
 
@@ -268,6 +273,7 @@ SPAN_DTYPE = np.dtype([("start", "<u4"), ("attr", "<u4")])
 CINTERVAL_DTYPE = np.dtype([("id", "<u4"), ("start", "<u4"), ("end", "<u4")])
 PATCH_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])
 PATCH_LOG_DTYPE = np.dtype([("status", "<u4"), ("n_patches", "<u4")])
+PATCH_CHECK_DTYPE = np.dtype([("status", "<u4"), ("agrees", "<u4"), ("n_patches", "<u4"), ("first_bad_record", "<u4"), ("digest", "<u8", (2,))])
 ROOT_ENTRY_DTYPE = np.dtype([("obj", "<u8"), ("key", "<u4"), ("row", "<u4"), ("kind", "<u4"), ("value", "<u4")])
 ROOT_LOG_DTYPE = np.dtype([("status", "<u4"), ("n_entries", "<u4"), ("first_bad_row", "<u4"), ("reserved", "<u4")])
 
@@ -318,6 +324,9 @@ FUNCTIONS = {
     "ptx_replay_patches": (C.c_int32, [vp, vp, vp, C.POINTER(ptx_patches)]),
     "ptx_replay_patches_from": (C.c_int32, [vp, vp, vp, vp, C.POINTER(ptx_patches)]),
     "ptx_patches_free": (None, [C.POINTER(ptx_patches)]),
+    "ptx_accumulate_patches": (C.c_int32, [vp, vp, C.POINTER(ptx_patches), C.POINTER(ptx_result)]),
+    "ptx_check_patches": (C.c_int32, [vp, vp, vp, C.POINTER(ptx_patch_check_log), u64p]),
+    "ptx_check_patches_ms": (C.c_int32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ptx_root_map": (C.c_int32, [vp, vp, C.POINTER(ptx_root_maps)]),
     "ptx_root_maps_free": (None, [C.POINTER(ptx_root_maps)]),
     "ptx_generate": (C.c_int32, [vp, C.POINTER(ptx_gen_config), C.POINTER(vp), C.POINTER(ptx_gen_info)]),

@@ -34,6 +34,7 @@
 #include "cursor_core.h"
 #include "rootmap_core.h"
 #include "sync_core.h"
+#include "accum_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -198,6 +199,17 @@ extern "C" __global__ void __launch_bounds__(64) ptx_sync_plan_kernel(PtxSyncArg
 }
 extern "C" __global__ void __launch_bounds__(PTX_SYNC_GATHER_THREADS) ptx_sync_gather_kernel(PtxSyncArgs A, PtxSyncGatherArgs G) {
     if (blockIdx.x < A.n_pairs) ptx_sync_gather_pair<PTX_SYNC_GATHER_THREADS>(A, G, blockIdx.x);
+}
+
+/* patch streams back into canonical rows (accum_core.h): one wave per log, the state in the log's LDS window or — a log beyond one CU's LDS, or
+ * PTX_FLAG_ACCUM_HBM_STATE — in a slice of global scratch; the same walk */
+extern "C" __global__ void __launch_bounds__(64) ptx_accum_kernel(PtxAccumArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
+    if (blockIdx.x < A.n_launch) ptx_accum_log<64>(A, blockIdx.x, ptx_lds);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_accum_kernel_hbm(PtxAccumArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_accum_lds[PTX_ACCUM_HBM_LDS_BYTES];
+    if (blockIdx.x < A.n_launch) ptx_accum_log_hbm<64>(A, blockIdx.x, ptx_accum_lds);
 }
 
 /* the map objects of a replica (rootmap_core.h): one wave per replica log; a first kernel counts the map rows (capacity of the entry rows) */
@@ -559,6 +571,7 @@ struct ptx_ctx {
     int force_lds = 0;     /* ptx_set_launch_shape: LDS window per log (0 = the library's choice) */
     int stop_after = 0;    /* -DPTX_DIAG builds only (ptx_diag_stop_after): truncate the diagnostic kernel after a phase, for per-phase PMC deltas */
     uint32_t flags = 0;
+    float check_replay_ms = 0.f, check_accum_ms = 0.f; /* the last ptx_check_patches (ptx_check_patches_ms) */
     unsigned long long* clocks = nullptr; /* device [PTX_NCLK], non-null only while ptx_merge_phase_cycles runs */
     /* staging of the SMALL result downloads (an editor session reads one replica per flush): a device block and a pinned host block that the context keeps and
      * grows on demand — a hipMalloc / hipFree (a device-wide wait) / hipHostMalloc / hipHostFree per read cost more than the read */
@@ -949,7 +962,7 @@ ptx_status ptx_create(int device_ordinal, uint32_t flags, ptx_ctx** out) {
     ctx->own_stream = ctx->stream;
     /* one workgroup may use the CU's whole 160 KiB of LDS */
     {
-        const void* kernels[] = {(const void*)ptx_merge_kernel, (const void*)ptx_merge_kernel_rest, (const void*)ptx_merge_kernel_many, (const void*)ptx_merge_kernel_many_wide, (const void*)ptx_merge_kernel_diag, (const void*)ptx_merge_kernel_w7, (const void*)ptx_merge_kernel_rest_w7, (const void*)ptx_merge_kernel_lean64, (const void*)ptx_merge_kernel_lean128, (const void*)ptx_merge_kernel_lean192, (const void*)ptx_merge_kernel_lean256, (const void*)ptx_replay_kernel, (const void*)ptx_replay_kernel_gwin, (const void*)ptx_replay_kernel_wide, (const void*)ptx_gen_kernel, (const void*)ptx_gen_kernel_r8, (const void*)ptx_change_kernel, (const void*)ptx_cursor_kernel, (const void*)ptx_rootmap_kernel, (const void*)ptx_sync_plan_kernel};
+        const void* kernels[] = {(const void*)ptx_merge_kernel, (const void*)ptx_merge_kernel_rest, (const void*)ptx_merge_kernel_many, (const void*)ptx_merge_kernel_many_wide, (const void*)ptx_merge_kernel_diag, (const void*)ptx_merge_kernel_w7, (const void*)ptx_merge_kernel_rest_w7, (const void*)ptx_merge_kernel_lean64, (const void*)ptx_merge_kernel_lean128, (const void*)ptx_merge_kernel_lean192, (const void*)ptx_merge_kernel_lean256, (const void*)ptx_replay_kernel, (const void*)ptx_replay_kernel_gwin, (const void*)ptx_replay_kernel_wide, (const void*)ptx_gen_kernel, (const void*)ptx_gen_kernel_r8, (const void*)ptx_change_kernel, (const void*)ptx_cursor_kernel, (const void*)ptx_rootmap_kernel, (const void*)ptx_sync_plan_kernel, (const void*)ptx_accum_kernel};
         e = hipSuccess;
         for (const void* k : kernels)
             if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds);
@@ -1946,7 +1959,117 @@ void ptx_patches_free(ptx_patches* p) {
 
 ptx_status ptx_replay_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, ptx_patches* out) { return ptx_replay_patches_from(ctx, b, r, nullptr, out); }
 
+/* who takes the packed records of a replay instead of the host (ptx_check_patches): the accumulate kernels, on every packed range while it sits on the device */
+struct PtxAccumSink {
+    const ptx_dresult* want;      /* the merge's result the streams are compared with */
+    ptx_patch_check_log* d_check; /* device [n_logs] */
+    float accum_ms;               /* HIP-event time of the accumulate launches, summed over the ranges */
+};
+/* the device blocks of the accumulate launches: made once per call, for its largest range (the chunked pack path has a range per few logs) */
+struct PtxAccumScratch {
+    uint32_t *d_idx = nullptr, *d_state = nullptr;
+    uint64_t* d_soff = nullptr;
+    uint64_t idx_cap = 0, state_units = 0;
+};
+static void accum_scratch_free(PtxAccumScratch* sc) {
+    (void)ptx_dev_free(sc->d_idx);
+    (void)ptx_dev_free(sc->d_state);
+    (void)ptx_dev_free(sc->d_soff);
+    *sc = PtxAccumScratch();
+}
+/* which state store a log takes: the slice of global scratch where its state exceeds one CU's LDS — or always, PTX_FLAG_ACCUM_HBM_STATE */
+static bool accum_log_to_hbm(const ptx_ctx* ctx, uint64_t rows, const ptx_log_hdr& h) { return (ctx->flags & PTX_FLAG_ACCUM_HBM_STATE) != 0 || ptx_accum_lds_need_hdr(rows, h) > ctx->max_lds; }
+static uint64_t accum_slice_units(uint64_t rows, const ptx_log_hdr& h) { return (ptx_accum_units_hdr(rows, h) + 31u) & ~31ull; } /* (slices do not share a cache line) */
+/* room for the logs [l0, l1): never shrinks; a call that knows its ranges asks for the largest first */
+static hipError_t accum_scratch_reserve(PtxAccumScratch* sc, uint64_t n_logs, uint64_t state_units) {
+    hipError_t e = hipSuccess;
+    if (n_logs > sc->idx_cap) {
+        (void)ptx_dev_free(sc->d_idx);
+        (void)ptx_dev_free(sc->d_soff);
+        sc->d_idx = nullptr, sc->d_soff = nullptr, sc->idx_cap = 0;
+        e = ptx_dev_malloc((void**)&sc->d_idx, n_logs * 4);
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&sc->d_soff, (n_logs + 1) * 8);
+        if (e == hipSuccess) sc->idx_cap = n_logs;
+    }
+    if (e == hipSuccess && state_units > sc->state_units) {
+        (void)ptx_dev_free(sc->d_state);
+        sc->d_state = nullptr, sc->state_units = 0;
+        e = ptx_dev_malloc((void**)&sc->d_state, 4 * state_units + 128);
+        if (e == hipSuccess) sc->state_units = state_units;
+    }
+    return e;
+}
+static uint64_t accum_range_state_units(const ptx_ctx* ctx, const std::vector<ptx_log_hdr>& hdr, const std::vector<uint64_t>& log_off, uint32_t l0, uint32_t l1) {
+    uint64_t units = 0;
+    for (uint32_t l = l0; l < l1; ++l)
+        if (accum_log_to_hbm(ctx, log_off[l + 1] - log_off[l], hdr[l])) units += accum_slice_units(log_off[l + 1] - log_off[l], hdr[l]);
+    return units;
+}
+/* The accumulate launches for the logs [l0, l1): those whose state fits the LDS in one launch of ptx_accum_kernel (its window = the largest of them), the others
+ * — or all, PTX_FLAG_ACCUM_HBM_STATE — in one of ptx_accum_kernel_hbm with a state slice each.  A = everything but the launch's own fields.  Waits for the
+ * stream (the caller fills the record buffer and this scratch again); *ms += the launches' HIP-event time when asked for (the context's two events: the
+ * replay's time has been read by then). */
+static ptx_status accum_launch_range(ptx_ctx* ctx, PtxAccumScratch* sc, const std::vector<ptx_log_hdr>& hdr, const std::vector<uint64_t>& log_off, uint32_t l0, uint32_t l1, PtxAccumArgs A,
+                                     float* ms) {
+    if (l1 <= l0) return PTX_OK;
+    std::vector<uint32_t> lds_logs, hbm_logs;
+    std::vector<uint64_t> soff(1, 0);
+    uint64_t need = 0;
+    for (uint32_t l = l0; l < l1; ++l) {
+        const uint64_t rows = log_off[l + 1] - log_off[l];
+        if (accum_log_to_hbm(ctx, rows, hdr[l])) {
+            hbm_logs.push_back(l);
+            soff.push_back(soff.back() + accum_slice_units(rows, hdr[l]));
+        } else {
+            lds_logs.push_back(l);
+            need = std::max(need, ptx_accum_lds_need_hdr(rows, hdr[l]));
+        }
+    }
+    const uint32_t n_lds = (uint32_t)lds_logs.size(), n_hbm = (uint32_t)hbm_logs.size();
+    const uint32_t lds_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, ctx->max_lds);
+    std::vector<uint32_t> idx(lds_logs);
+    idx.insert(idx.end(), hbm_logs.begin(), hbm_logs.end());
+    hipError_t e = accum_scratch_reserve(sc, idx.size(), soff[n_hbm]);
+    if (e == hipSuccess) e = hipMemcpyAsync(sc->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n_hbm) e = hipMemcpyAsync(sc->d_soff, soff.data(), ((size_t)n_hbm + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && ms) e = hipEventRecord(ctx->ev0, ctx->stream);
+    if (e == hipSuccess && n_lds) {
+        A.first_log = 0;
+        A.n_launch = n_lds;
+        A.log_index = sc->d_idx;
+        A.state = nullptr;
+        A.state_off = nullptr;
+        A.lds_bytes = lds_bytes;
+        hipLaunchKernelGGL(ptx_accum_kernel, dim3(n_lds), dim3(64), lds_bytes, ctx->stream, A);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && n_hbm) {
+        A.first_log = 0;
+        A.n_launch = n_hbm;
+        A.log_index = sc->d_idx + n_lds;
+        A.state = (uint32_t*)(((uintptr_t)sc->d_state + 127u) & ~(uintptr_t)127u);
+        A.state_off = sc->d_soff;
+        A.lds_bytes = PTX_ACCUM_HBM_LDS_BYTES;
+        hipLaunchKernelGGL(ptx_accum_kernel_hbm, dim3(n_hbm), dim3(64), 0, ctx->stream, A);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && ms) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* (idx / soff are pageable host memory of this frame, and the caller reuses the blocks) */
+    if (e == hipSuccess && ms) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, ctx->ev0, ctx->ev1) == hipSuccess) *ms += t;
+    }
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("ptx_accum_kernel: ") + hipGetErrorString(e));
+    return PTX_OK;
+}
+
+static ptx_status replay_patches_impl(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const uint32_t* first_row, ptx_patches* out, PtxAccumSink* sink);
 ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const uint32_t* first_row, ptx_patches* out) {
+    return replay_patches_impl(ctx, b, r, first_row, out, nullptr);
+}
+
+/* the replay; with a sink the packed records of every range go to the accumulate kernels instead of the host: no record download, no host room for them */
+static ptx_status replay_patches_impl(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const uint32_t* first_row, ptx_patches* out, PtxAccumSink* sink) {
     if (!ctx || !b || !r || !out) return PTX_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
     if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
@@ -2178,12 +2301,46 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
                 pack_cap = std::max<uint64_t>(pack_cap / 2, longest);
             }
             if (e == hipSuccess) e = hipMemcpyAsync(d_xoff, xoff.data(), ((size_t)L + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-            h->patches.resize(std::max<uint64_t>(xtotal, 1));
+            h->patches.resize(sink ? 1 : std::max<uint64_t>(xtotal, 1));
+            PtxAccumScratch scratch;
+            if (sink && e == hipSuccess) { /* the accumulate launches' blocks, once, for the largest of the ranges below */
+                uint64_t most_logs = 0, most_units = 0;
+                for (uint32_t l0 = 0; l0 < L;) {
+                    uint32_t l1 = l0 + 1;
+                    while (l1 < L && xoff[l1 + 1] - xoff[l0] <= pack_cap) ++l1;
+                    most_logs = std::max<uint64_t>(most_logs, l1 - l0);
+                    most_units = std::max(most_units, accum_range_state_units(ctx, hdr, log_off, l0, l1));
+                    l0 = l1;
+                }
+                e = accum_scratch_reserve(&scratch, most_logs, most_units);
+            }
             for (uint32_t l0 = 0; e == hipSuccess && l0 < L;) {
                 uint32_t l1 = l0 + 1;
                 while (l1 < L && xoff[l1 + 1] - xoff[l0] <= pack_cap) ++l1;
                 const uint64_t cnt = xoff[l1] - xoff[l0];
-                if (cnt) {
+                if (sink) { /* the range is accumulated where it sits (a log without records has a row of its own too) */
+                    if (cnt) {
+                        hipLaunchKernelGGL(ptx_patch_pack_kernel, dim3(l1 - l0), dim3(256), 0, ctx->stream, d_patches, d_off, d_ext, d_xoff, d_packed, l0, xoff[l0]);
+                        e = hipGetLastError();
+                    }
+                    if (e == hipSuccess) {
+                        PtxAccumArgs AA;
+                        memset(&AA, 0, sizeof(AA));
+                        AA.log_off = b->log_off;
+                        AA.payload = b->payload;
+                        AA.action = b->action;
+                        AA.mark_type = b->mark_type;
+                        AA.log_hdr = b->log_hdr;
+                        AA.patches = d_packed;
+                        AA.rec_off = d_xoff;
+                        AA.rec_base = xoff[l0];
+                        AA.plogs = d_logs;
+                        AA.want = sink->want->logs;
+                        AA.check = sink->d_check;
+                        st = accum_launch_range(ctx, &scratch, hdr, log_off, l0, l1, AA, &sink->accum_ms); /* (waits: the buffer is filled again) */
+                        if (st != PTX_OK) break;
+                    }
+                } else if (cnt) {
                     hipLaunchKernelGGL(ptx_patch_pack_kernel, dim3(l1 - l0), dim3(256), 0, ctx->stream, d_patches, d_off, d_ext, d_xoff, d_packed, l0, xoff[l0]);
                     e = hipGetLastError();
                     if (e == hipSuccess) e = hipMemcpyAsync(h->patches.data() + xoff[l0], d_packed, cnt * sizeof(ptx_patch), hipMemcpyDeviceToHost, ctx->stream);
@@ -2192,7 +2349,8 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
                 l0 = l1;
             }
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) st = fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("patch download: ") + hipGetErrorString(e));
+            accum_scratch_free(&scratch);
+            if (e != hipSuccess && st == PTX_OK) st = fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("patch download: ") + hipGetErrorString(e));
             h->off = xoff;
             break;
         }
@@ -2209,6 +2367,109 @@ ptx_status ptx_replay_patches_from(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_
     out->patch_off = h->off.data();
     out->logs = h->logs.data();
     out->patches = h->patches.data();
+    return PTX_OK;
+}
+
+/* ---- patch streams back into canonical rows (accum_core.h) ---- */
+ptx_status ptx_accumulate_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_patches* p, ptx_result* out) {
+    if (!ctx || !b || !p || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    const uint32_t L = b->n_logs;
+    if (p->n_logs != L) return fail(ctx, PTX_ERR_INVALID_ARG, "the patch streams do not match the batch");
+    if (L && (!p->patch_off || !p->logs)) return fail(ctx, PTX_ERR_INVALID_ARG, "patch_off / logs missing");
+    const uint64_t total = L ? p->patch_off[L] : 0;
+    for (uint32_t l = 0; l < L; ++l)
+        if (p->logs[l].status == PTX_OK && (p->patch_off[l] > total || p->logs[l].n_patches > total - p->patch_off[l]))
+            return fail(ctx, PTX_ERR_INVALID_ARG, "a log's records run past patch_off[n_logs]");
+    if (total && !p->patches) return fail(ctx, PTX_ERR_INVALID_ARG, "patches missing");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_dresult tmp; /* rows where the merge's go; no elem_rank */
+    tmp.n_logs = L;
+    tmp.n_rows = b->n_ops;
+    std::vector<ptx_log_hdr> hdr(L);
+    std::vector<uint64_t> log_off((size_t)L + 1, 0);
+    ptx_patch* d_pat = nullptr;
+    uint64_t* d_poff = nullptr;
+    ptx_patch_log* d_plogs = nullptr;
+    hipError_t e = dalloc(&tmp.logs, L);
+    if (e == hipSuccess) e = dalloc(&tmp.values, tmp.n_rows);
+    if (e == hipSuccess) e = dalloc(&tmp.spans, tmp.n_rows);
+    if (e == hipSuccess) e = dalloc(&tmp.cints, tmp.n_rows);
+    if (e == hipSuccess) e = dalloc(&d_pat, total);
+    if (e == hipSuccess) e = dalloc(&d_poff, (uint64_t)L + 1);
+    if (e == hipSuccess) e = dalloc(&d_plogs, L);
+    if (e == hipSuccess && L) e = hipMemcpyAsync(hdr.data(), b->log_hdr, (size_t)L * sizeof(ptx_log_hdr), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && L) e = hipMemcpyAsync(log_off.data(), b->log_off, ((size_t)L + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(d_pat, p->patches, total * sizeof(ptx_patch), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && L) e = hipMemcpyAsync(d_poff, p->patch_off, ((size_t)L + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && L) e = hipMemcpyAsync(d_plogs, p->logs, (size_t)L * sizeof(ptx_patch_log), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    ptx_status st = e == hipSuccess ? PTX_OK : fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("ptx_accumulate_patches set-up: ") + hipGetErrorString(e));
+    if (st == PTX_OK && L) {
+        PtxAccumArgs A;
+        memset(&A, 0, sizeof(A));
+        A.log_off = b->log_off;
+        A.payload = b->payload;
+        A.action = b->action;
+        A.mark_type = b->mark_type;
+        A.log_hdr = b->log_hdr;
+        A.patches = d_pat;
+        A.rec_off = d_poff;
+        A.rec_base = 0;
+        A.plogs = d_plogs;
+        A.res = tmp.logs;
+        A.out_values = tmp.values;
+        A.out_spans = tmp.spans;
+        A.out_cints = tmp.cints;
+        PtxAccumScratch scratch;
+        st = accum_launch_range(ctx, &scratch, hdr, log_off, 0, L, A, nullptr);
+        accum_scratch_free(&scratch);
+    }
+    if (st == PTX_OK) st = ptx_result_download(ctx, b, &tmp, out);
+    (void)ptx_dev_free(tmp.logs);
+    (void)ptx_dev_free(tmp.values);
+    (void)ptx_dev_free(tmp.spans);
+    (void)ptx_dev_free(tmp.cints);
+    (void)ptx_dev_free(d_pat);
+    (void)ptx_dev_free(d_poff);
+    (void)ptx_dev_free(d_plogs);
+    return st;
+}
+
+ptx_status ptx_check_patches(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, ptx_patch_check_log* out, uint64_t* n_disagree) {
+    if (!ctx || !b || !r || !out || !n_disagree) return PTX_ERR_INVALID_ARG;
+    *n_disagree = 0;
+    const uint32_t L = b->n_logs;
+    if (r->n_logs != L || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
+    if (!r->rank) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_check_patches needs the elem_rank column (context created with PTX_FLAG_NO_ELEM_RANK)");
+    if (L == 0) return PTX_OK;
+    PTX_HIP(ctx, ptx_enter(ctx));
+    PtxAccumSink sink;
+    sink.want = r;
+    sink.d_check = nullptr;
+    sink.accum_ms = 0.f;
+    PTX_HIP(ctx, dalloc(&sink.d_check, L));
+    ptx_patches pat;
+    ptx_status st = replay_patches_impl(ctx, b, r, nullptr, &pat, &sink);
+    if (st == PTX_OK) {
+        ctx->check_replay_ms = pat.kernel_ms;
+        ctx->check_accum_ms = sink.accum_ms;
+        ptx_patches_free(&pat);
+        /* the one download of the answer: 32 bytes per log */
+        hipError_t e = hipMemcpyAsync(out, sink.d_check, (size_t)L * sizeof(ptx_patch_check_log), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) st = fail(ctx, PTX_ERR_HIP, std::string("ptx_check_patches download: ") + hipGetErrorString(e));
+    }
+    (void)ptx_dev_free(sink.d_check);
+    if (st == PTX_OK)
+        for (uint32_t l = 0; l < L; ++l) *n_disagree += out[l].status == PTX_OK && out[l].agrees == 0u ? 1u : 0u;
+    return st;
+}
+
+ptx_status ptx_check_patches_ms(const ptx_ctx* ctx, float* replay_ms, float* accum_ms) {
+    if (!ctx || !replay_ms || !accum_ms) return PTX_ERR_INVALID_ARG;
+    *replay_ms = ctx->check_replay_ms;
+    *accum_ms = ctx->check_accum_ms;
     return PTX_OK;
 }
 

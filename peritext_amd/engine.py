@@ -315,6 +315,44 @@ class Engine:
         finally:
             self.lib.ptx_patches_free(C.byref(p))
 
+    def accumulate_patches(self, dbatch, pat):
+        """Patch streams of any origin (wire.Patches: this library's replay, or records a peer sent) turned back into the canonical rows of the documents
+        they describe — reference/test/accumulatePatches.ts on the device (ptx_accumulate_patches).  Returns what `download` returns (no elem_rank); a
+        log whose stream is malformed reports PTX_ERR_INDEX_OOB / BAD_OP / CAPACITY and the index of its first bad record in reserved[1]."""
+        n = self.n_logs(dbatch)
+        off = np.ascontiguousarray(pat.patch_off, dtype=np.uint64)
+        logs = np.ascontiguousarray(pat.logs, dtype=abi.PATCH_LOG_DTYPE)
+        rows = np.ascontiguousarray(pat.patches, dtype=abi.PATCH_DTYPE)
+        if len(logs) != n or len(off) != n + 1 or len(rows) < int(off[n]):
+            raise ValueError("the patch streams do not match the batch")
+        p = abi.ptx_patches()
+        p.n_logs = n
+        p.patch_off = off.ctypes.data_as(abi.u64p)
+        p.logs = logs.ctypes.data_as(C.POINTER(abi.ptx_patch_log))
+        p.patches = rows.ctypes.data_as(C.POINTER(abi.ptx_patch))
+        res = abi.ptx_result()
+        self._check(self.lib.ptx_accumulate_patches(self.ctx, dbatch, C.byref(p), C.byref(res)))
+        try:
+            return _copy_result(res)
+        finally:
+            self.lib.ptx_result_free(C.byref(res))
+
+    def check_patches(self, dbatch, dresult):
+        """The fuzzer's patch assertion (reference/test/fuzz.ts:245-278) for every log of a resident batch, on the device: replay, accumulate the records
+        where they were written, compare with the merge `dresult` (ptx_check_patches; no record is downloaded).  Returns (rows, n_disagree): rows =
+        PATCH_CHECK_DTYPE [n_logs] {status, agrees, n_patches, first_bad_record, digest}, n_disagree = the logs with status 0 and agrees == 0."""
+        n = self.n_logs(dbatch)
+        rows = np.zeros(max(n, 1), dtype=abi.PATCH_CHECK_DTYPE)
+        bad = C.c_uint64(0)
+        self._check(self.lib.ptx_check_patches(self.ctx, dbatch, dresult, rows.ctypes.data_as(C.POINTER(abi.ptx_patch_check_log)), C.byref(bad)))
+        return rows[:n], int(bad.value)
+
+    def check_patches_ms(self):
+        """(replay_ms, accum_ms): HIP-event durations of the kernels of the last check_patches: the replay launches of its last replay attempt only, and the accumulate launches summed over the packed ranges."""
+        a, b = C.c_float(0), C.c_float(0)
+        self._check(self.lib.ptx_check_patches_ms(self.ctx, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     def generate(self, replicas, ops_per_log, mix, mark_types, n_docs, seed, first_doc=0, list_cap=0, initial_text=""):
         """On-device change(): n_docs PTXGEN documents (oracle/ptxgen.js, i.e. the workload of reference/test/fuzz.ts)
         generated straight into HBM.  Returns (resident batch handle, {"kernel_ms", "n_comments"})."""

@@ -78,6 +78,9 @@ struct Lib {
     ptx_status (*device_alloc)(ptx_ctx*, uint64_t, void**) = nullptr;
     void (*device_free)(ptx_ctx*, void*) = nullptr;
     ptx_status (*device_read)(ptx_ctx*, const void*, void*, uint64_t) = nullptr;
+    /* patch streams back into canonical rows; the fuzzer's patch assertion on the device */
+    ptx_status (*accumulate_patches)(ptx_ctx*, const ptx_dbatch*, const ptx_patches*, ptx_result*) = nullptr;
+    ptx_status (*check_patches)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, ptx_patch_check_log*, uint64_t*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -125,7 +128,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.allgather_digests, "ptx_allgather_digests") && sym(L.count_converged_digests, "ptx_count_converged_digests") &&
                   sym(L.result_download_logs, "ptx_result_download_logs") && sym(L.root_map, "ptx_root_map") && sym(L.root_maps_free, "ptx_root_maps_free") && sym(L.device_alloc, "ptx_device_alloc") && sym(L.device_free, "ptx_device_free") &&
                   sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device") &&
-                  sym(L.sync_replicas, "ptx_sync_replicas");
+                  sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -937,6 +940,72 @@ napi_value MergeAndGather(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* accumulatePatches(ctx, batch, streams: {patchOff: BigUint64Array(nLogs + 1), patchLogs: Uint32Array(2 per log), patches: Uint32Array(4 per record)}) -> the
+ * result object of applyMaterialize (no elemRank): the documents the streams describe (ptx_accumulate_patches) */
+napi_value AccumulatePatches(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    if (!ctx) return throw_msg(env, "accumulatePatches(ctx, batch, streams)");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    const void *off = nullptr, *logs = nullptr, *recs = nullptr;
+    size_t n_off = 0, n_logs = 0, n_recs = 0;
+    if (!column(env, argv[2], "patchOff", 8, &off, &n_off) || !column(env, argv[2], "patchLogs", 4, &logs, &n_logs) || !column(env, argv[2], "patches", 4, &recs, &n_recs) ||
+        n_off != (size_t)pb.n_logs + 1 || n_logs != (size_t)pb.n_logs * 2 || (uint64_t)n_recs < ((const uint64_t*)off)[pb.n_logs] * 4)
+        return throw_msg(env, "accumulatePatches: streams need patchOff (BigUint64Array, nLogs + 1), patchLogs (Uint32Array, 2 per log) and patches (Uint32Array, 4 per record)");
+    ptx_patches pat;
+    memset(&pat, 0, sizeof(pat));
+    pat.n_logs = pb.n_logs;
+    pat.patch_off = (const uint64_t*)off;
+    pat.logs = (const ptx_patch_log*)logs;
+    pat.patches = (const ptx_patch*)recs;
+    ptx_dbatch* db = nullptr;
+    ptx_result res;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.accumulate_patches(ctx, db, &pat, &res);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) return throw_msg(env, ("accumulatePatches failed: " + err).c_str());
+    return result_to_js(env, res, nullptr);
+}
+
+/* checkPatches(ctx, batch) -> {rows: Uint32Array (8 per log: status, agrees, nPatches, firstBadRecord, digest as 4 x u32), disagree}: merge, replay and
+ * accumulate on the device, the streams compared with the merge there (ptx_check_patches) */
+napi_value CheckPatches(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 1 ? ctx_of(env, argv[0]) : nullptr;
+    if (!ctx) return throw_msg(env, "checkPatches(ctx, batch)");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    static_assert(sizeof(ptx_patch_check_log) == 32, "ptx_patch_check_log layout");
+    std::vector<ptx_patch_check_log> rows(pb.n_logs ? pb.n_logs : 1);
+    uint64_t disagree = 0;
+    ptx_dbatch* db = nullptr;
+    ptx_dresult* dr = nullptr;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.result_alloc(ctx, db, &dr);
+    if (st == PTX_OK) st = L.merge(ctx, db, dr);
+    if (st == PTX_OK) st = L.sync(ctx);
+    if (st == PTX_OK) st = L.check_patches(ctx, db, dr, rows.data(), &disagree);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (dr) L.dresult_free(ctx, dr);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) return throw_msg(env, ("checkPatches failed: " + err).c_str());
+    napi_value out, v;
+    NAPI_OK(napi_create_object(env, &out));
+    v = make_u32(env, rows.data(), (size_t)pb.n_logs * 8);
+    if (v) napi_set_named_property(env, out, "rows", v);
+    napi_create_double(env, (double)disagree, &v);
+    napi_set_named_property(env, out, "disagree", v);
+    return out;
+}
+
 napi_value MaxOpsPerLog(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
@@ -965,7 +1034,9 @@ napi_value Init(napi_env env, napi_value exports) {
     }
     /* the enumerable exports above are the list the host's load check pins (tests/test_node_host.py); entry points added since are defined beside them as plain
      * (non-enumerable) properties: index.js calls them by name */
-    const napi_property_descriptor later[] = {{"syncReplicas", nullptr, SyncReplicas, nullptr, nullptr, nullptr, napi_default, nullptr}};
+    const napi_property_descriptor later[] = {{"syncReplicas", nullptr, SyncReplicas, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"accumulatePatches", nullptr, AccumulatePatches, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"checkPatches", nullptr, CheckPatches, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

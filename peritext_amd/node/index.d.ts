@@ -123,6 +123,10 @@ export class MergeEngine {
     applyChanges(docs: Change[][][], opts?: { listKeys: string[] }): FormatSpanWithText[][][] | Array<Array<{ [key: string]: FormatSpanWithText[] }>>
     /** spans as applyChanges + patches[doc][replica][change] = what applyChange(change) returns (micromerge.ts:499) */
     applyChangesWithPatches(docs: Change[][][]): { spans: FormatSpanWithText[][][]; patches: Patch[][][][] }
+    /** patch streams (patchOff / patchLogs / patches of `res`: this library's, or a peer's) back into the documents they describe (ptx_accumulate_patches) */
+    accumulatePatches(batch: WireBatch, res: { patchOff: BigUint64Array; patchLogs: Uint32Array; patches: Uint32Array }): WireResult
+    /** the fuzzer's patch assertion on the device (ptx_check_patches): status[doc][replica], agrees[doc][replica], disagree = streams that do not rebuild their merged document */
+    checkPatches(docs: Change[][][]): { status: number[][]; agrees: boolean[][]; disagree: number }
     /** getRoot() of every replica: roots[doc][replica] (ptx_root_map) */
     roots(docs: Change[][][]): RootJson[][]
     /** on-device change(): edit histories generated on the GPU (ptx_generate; the documents of oracle/ptxgen.js for the same seed) and merged there */

@@ -758,6 +758,25 @@ class MergeEngine {
             patches: docs.map(logs => logs.map(() => decodePatches(batch, res, log2++))),
         }
     }
+    /** The consumer side of the patch API (ptx_accumulate_patches; reference/test/accumulatePatches.ts on the device): `res` holds patch streams of the
+     *  logs of `batch` — patchOff / patchLogs / patches as applyMaterialize(batch, true) returns them, or records a peer sent — and the return value is the
+     *  WireResult of the documents they describe (decodeSpans reads it).  A malformed stream fails its own log only: status 5 / 6 / 7 in its row. */
+    accumulatePatches(batch, res) {
+        return this.addon.accumulatePatches(this.ctx, batch, res)
+    }
+    /** The patch assertion of the reference's fuzzer (test/fuzz.ts:245-278) for every replica: merge, replay and accumulate on the device, compare there
+     *  (ptx_check_patches; no record comes back).  docs: Change[][][] -> {status[d][r], agrees[d][r], disagree = replicas with status 0 whose stream does
+     *  not rebuild the merged document}. */
+    checkPatches(docs) {
+        const batch = encodeDocs(docs)
+        const raw = this.addon.checkPatches(this.ctx, batch)
+        let log = 0, log2 = 0
+        return {
+            status: docs.map(logs => logs.map(() => raw.rows[8 * log++])),
+            agrees: docs.map(logs => logs.map(() => raw.rows[8 * log2++ + 1] === 1)),
+            disagree: raw.disagree,
+        }
+    }
     /** docs: Change[][][] -> getRoot() of every replica (ptx_root_map: the root map and the maps nested in it, last writer wins per
      *  key, micromerge.ts:572-602; list objects appear as { $list: true }).  A replica the reference would have thrown on
      *  ("Object does not exist") throws a RangeError here too. */
