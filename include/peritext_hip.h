@@ -281,6 +281,11 @@ typedef struct ptx_dresult ptx_dresult;  /* result buffers resident in HBM */
                                         state does not fit one CU's LDS); tests / measurement */
 #define PTX_FLAG_PAD_GATHER 4u   /* ptx_allgather_digests always takes its padded path (pack, all-gather of max(counts) pairs per rank, compact on the
                                     device) even when every rank holds the same number of logs: same result; lets a one-GPU host exercise that path */
+#define PTX_FLAG_READMIT 64u     /* ptx_merge walks the Change envelope of every log in EVERY launch, as the library did before it kept admission marks, and leaves
+                                    the marks of the batch alone.  By default a resident batch remembers, per log, the prefix of changes whose seq / deps checks
+                                    passed in an earlier launch of any context (its columns never change, so they pass again) and a launch walks only the changes
+                                    behind it: none for a batch merged before, the appended ones for a batch grown by ptx_batch_append[_device].  Results are the
+                                    same either way; a log that fails is walked and reported again in every launch.  For measurement and tests */
 
 /* ---- lifecycle ---- */
 uint32_t ptx_abi_version(void);
@@ -304,7 +309,8 @@ ptx_status ptx_batch_upload(ptx_ctx* ctx, const ptx_batch* host, ptx_dbatch** ou
 /* Build a resident batch made of `copies` back-to-back copies of `host` (distinct HBM addresses,
  * used to scale a synthetic batch to BASELINE sizes without regenerating it). */
 ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* host, uint32_t copies, ptx_dbatch** out);
-/* Adopt caller-owned DEVICE pointers (e.g. torch tensors' data_ptr); nothing is copied or freed. */
+/* Adopt caller-owned DEVICE pointers (e.g. torch tensors' data_ptr); nothing is copied or freed.  (The caller may rewrite that memory between merges: such a
+ * batch keeps no admission marks, see ptx_merge.) */
 ptx_status ptx_batch_wrap_device(ptx_ctx* ctx, const ptx_batch* device, ptx_dbatch** out);
 /* Streaming append: a NEW resident batch whose log l = log l of `base` followed by log l of `more` (host
  * pointers; the changes that arrived since, in application order; same n_logs, empty logs allowed).  Rows are copied
@@ -324,7 +330,15 @@ void ptx_batch_launch_shape(const ptx_dbatch* b, uint32_t* threads, uint32_t* ld
 ptx_status ptx_result_alloc(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult** out);
 void ptx_dresult_free(ptx_ctx* ctx, ptx_dresult* r);
 
-/* Enqueue the merge of every log of `b` on the context's stream (asynchronous). */
+/* Enqueue the merge of every log of `b` on the context's stream (asynchronous).
+ * Causal admission is kept, not repeated: a batch the library made with the Change envelope (upload, append, generate, ptx_change, ptx_sync_replicas — not
+ * ptx_batch_wrap_device, whose memory is the caller's) carries one 16-byte ADMISSION MARK per log on the device — {changes admitted, their rows, the vector clock
+ * after them} — written by the first launch in which all of the log's changes pass applyChange's seq / deps checks (micromerge.ts:499-511: the reference, too,
+ * checks a change once, when it arrives, against a clock that is replica state).  A later launch of ANY context on that batch reads the mark instead of the
+ * envelope; ptx_batch_append[_device] hands the marks of `base` to the grown batch (documents of up to three actors), whose next launch checks the appended
+ * changes only.  This is the ONE thing a merge writes into a batch; a batch's columns stay immutable.  A log that fails writes no mark: it is walked, and fails
+ * with the same status and row, in every launch.  Results never depend on the marks (PTX_FLAG_READMIT: ignore them); launches on several streams may share a
+ * batch — a mark is one aligned 16-byte store, and every value a launch can read there is true. */
 ptx_status ptx_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r);
 /* Same, `iters` times back to back, bracketed by HIP events on the context's stream:
  * *ms_total = elapsed milliseconds of the `iters` launches (for roofline accounting). */

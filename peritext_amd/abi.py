@@ -33,6 +33,7 @@ FLAG_PAD_GATHER = 4
 FLAG_REPLAY_LDS_ONLY = 8
 FLAG_REPLAY_HBM_STATE = 16  # ptx_replay_patches: every log through the HBM-state kernel (a test and measurement knob)
 FLAG_ACCUM_HBM_STATE = 32  # ptx_accumulate_patches / ptx_check_patches: every log with its state in global scratch (a test and measurement knob)
+FLAG_READMIT = 64  # ptx_merge: walk every log's Change envelope in every launch and leave the batch's admission marks alone (measurement, tests)
 COMM_ID_BYTES = 128
 
 PTX_OK = 0

@@ -108,6 +108,16 @@
 #endif
 #include PTX_PLATFORM_HEADER
 
+/* ---- the admission mark of one log of a resident batch: what P0 has already admitted of it.  One 16-byte, 16-byte-aligned record per log in a device array
+ *      beside the batch (the library's own: zeroed when the batch is made, copied by an append while the batch has at most three actors), read with ONE 16-byte load
+ *      and written with ONE 16-byte store by one lane — a launch on another stream sees the old record or the new one
+ *      (and were it ever to see words of both, the one-pass check would fail and the exact walk decide: the argument stands at ptx_const_load, ptx_platform_gfx950.h).
+ *        x = changes_admitted   the first x changes of the log passed applyChange's checks (micromerge.ts:499-511) in an earlier launch
+ *        y = rows_covered       the op rows of those changes
+ *        z = clock[0] | clock[1] << 16,  w = clock[2]   the vector clock after them (documents of up to three actors; at most 65 533 changes per log: 16 bits each)
+ *      A batch's columns never change, so the checks of an admitted prefix need not be made again: x == C skips P0, 0 < x < C (a log grown by an append) walks the
+ *      suffix from the recorded clock.  A log that fails writes nothing and is walked from 0 in every launch. ---- */
+typedef uint32_t ptx_adm_mark __attribute__((vector_size(16)));
 
 /* kernel arguments: device pointers (host pointers in the test-suite's emulation) */
 struct PtxMergeArgs {
@@ -147,6 +157,8 @@ struct PtxMergeArgs {
     uint32_t* out_refs_hi; /* optional, beside out_refs: the HIGH halves of the boundary slots of the mark rows (start >> 16 | end >> 16 << 16; 0xFFFF beside a low half of
                               0xFFFF = none) — written by the HBM-staged kernel alone, for logs of more than 32 766 list elements, whose slots 2 rank + side pass 16 bits
                               (round 6: the replay and change() on such logs) */
+    ptx_adm_mark* adm_marks; /* optional [n_logs]: the admission marks of the batch (see ptx_adm_mark); nullptr = every change is walked, nothing is recorded (batches that
+                                do not own their columns, PTX_FLAG_READMIT, the diagnostic launches).  biglog_core.h ignores it */
 };
 
 #define PTX_END 0xFFFFu
@@ -769,6 +781,20 @@ PTX_DEV void ptx_adm_step_n(PtxAdmWaveN<kW>& S, uint32_t na, const uint32_t* h, 
     for (uint32_t j = 0; j < kW; ++j) S.b[j] += ptx_wave_last(incl[j]);
 }
 #define PTX_ADMN_WREC 28u /* words a wave leaves for the validation: b[kW], g[kW], mx[kW] (kW <= 8), known, bad, amax */
+/* LDS scratch of P0, in words per ptx_alloc call — ONE definition for the walks that allocate it and for the skip path of a marked log, which only accounts for it
+ * (ptx_adm_scratch_bytes: a log's LDS high-water mark, a diagnostic of its result row, must not depend on whether its walk ran in this launch) */
+#define PTX_ADM_WT_WORDS (PTX_MAX_THREADS / 64u + 2u)             /* three actors: per-wave clock totals of the exact walk, twice */
+#define PTX_ADM_WREC3_WORDS ((PTX_MAX_THREADS / 64u + 1u) * 12u)  /* three actors: the waves' check records + the spare one that holds the clock before the walk */
+#define PTX_ADM_WRECN_WORDS ((PTX_MAX_THREADS / 64u + 1u) * PTX_ADMN_WREC) /* four to fifteen actors: the waves' check records */
+#define PTX_ADM_FIRST_WORDS(na_) ((na_) + 2u)                     /* the table: first slot per actor ... */
+#define PTX_ADM_TBL_WORDS(C_) ((C_) + 1u)                         /* ... and (actor, seq) -> change */
+PTX_HD uint32_t ptx_adm_words_bytes(uint32_t words) { return (uint32_t)(((uint64_t)words * 4u + 15u) & ~15ull); } /* (what ptx_alloc<uint32_t> takes) */
+/* bytes P0 has allocated at its high-water mark for a log that PASSES: the one-pass walk's scratch, or the table's where there is no walk (kManyActors build, na actors) */
+PTX_HD uint32_t ptx_adm_scratch_bytes(int many_actors, uint32_t na, uint32_t C) {
+    if (na <= 3u) return 2u * ptx_adm_words_bytes(PTX_ADM_WT_WORDS) + ptx_adm_words_bytes(PTX_ADM_WREC3_WORDS);
+    const bool walk_n = many_actors == 2 ? na >= 8u && na <= 15u : na <= 7u;
+    return walk_n ? ptx_adm_words_bytes(PTX_ADM_WRECN_WORDS) : ptx_adm_words_bytes(PTX_ADM_FIRST_WORDS(na)) + ptx_adm_words_bytes(PTX_ADM_TBL_WORDS(C));
+}
 #define PTX_ADMN_HALF(w_, k_) (((w_)[(k_) >> 1] >> (16u * ((k_) & 1u))) & 0xFFFFu)
 
 /* the walk of one log: true = every change is admitted (the same answer in every thread; ends with the barrier after which wrec may be reused) */
@@ -952,10 +978,13 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
     constexpr bool kShort = kThreads == 64u || kThreads == 128u;
     uint64_t chg0_early = 0, chg1_early = 0;
     ptx_log_hdr hd_early = ptx_log_hdr();
+    constexpr bool kMarks = !kDiag; /* (the diagnostic builds neither read nor write admission marks: their "P0 admission" stamps keep measuring the walk) */
+    ptx_adm_mark mk = {0u, 0u, 0u, 0u};
     if (kShort) {
         if (A.chg_off) {
             chg0_early = A.chg_off[log];
             chg1_early = A.chg_off[log + 1];
+            if (kMarks && A.adm_marks) mk = PTX_CONST_LOAD(&A.adm_marks[log]);
         }
         hd_early = A.log_hdr[log];
     }
@@ -1077,6 +1106,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
      * (the census sends the others to biglog_core.h): a value saturated at 65535 can never be admitted here — the same error as
      * the true one. */
     if (A.chg_off) {
+        if (kMarks && !kShort && A.adm_marks) mk = PTX_CONST_LOAD(&A.adm_marks[log]); /* (beside the two offsets below: no trip of its own) */
         const uint64_t c0 = kShort ? chg0_early : A.chg_off[log];
         const uint64_t C64 = (kShort ? chg1_early : A.chg_off[log + 1]) - c0;
         const uint32_t na = A.max_actors;
@@ -1095,31 +1125,47 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         for (uint32_t q_ = 0; q_ < (c_); ++q_) r_ += c_hdr[q_] & PTX_CHG_NOPS; \
         (row_) = r_ < 65535u ? r_ : 65535u;                                   \
     } while (0)
-        if (na <= 3u) {
+        /* the log's admission mark: every change admitted before (the same columns: the same answer) -> no P0 at all, the path of a batch without envelope;
+         * a proper prefix admitted before (the log has grown by an append) -> the three-actor walk below starts behind it */
+        const bool adm_skip = kMarks && mk[0] == C && mk[1] == N && C != 0u && (na <= 3u || kManyActors != 0);
+        const uint32_t adm_from = kMarks && na <= 3u && mk[0] != 0u && mk[0] < C && mk[1] <= N ? mk[0] : 0u; /* (anything else, a record beyond the log included: from 0) */
+        if (adm_skip) {
+            /* no walk.  The LDS high-water mark of the result row (a diagnostic) counts the scratch of the walk that marked the log all the same: a log's row is
+             * the same in every launch */
+            const uint32_t p0 = ptx_adm_scratch_bytes(kManyActors, na, C);
+            if (bp.off + p0 > bp.high) bp.high = bp.off + p0;
+        } else if (na <= 3u) {
             /* Up to three actors (the usual case; envelope rows of 8 bytes): the vector clock itself is carried along the log.  Every WAVE owns a
              * contiguous segment of the changes and walks it 64 * PTX_AC changes at a time, PTX_AC consecutive changes per
              * lane, read with 16-byte loads (4 headers / 2 envelope rows each); inside a step the clock before each change
              * is a DPP prefix sum of one-hot counts, 16 bits per actor (actors 0,1 in one word, 2,3 in the other); the
              * clock before a wave's segment is the sum of the earlier waves' totals.  seq == clock[actor] + 1 and
              * deps[b] <= clock[b] (micromerge.ts:501-509) are then plain compares. */
-            uint32_t* wt01 = ptx_alloc<uint32_t>(bp, PTX_MAX_THREADS / 64 + 2);
-            uint32_t* wt23 = ptx_alloc<uint32_t>(bp, PTX_MAX_THREADS / 64 + 2);
+            uint32_t* wt01 = ptx_alloc<uint32_t>(bp, PTX_ADM_WT_WORDS);
+            uint32_t* wt23 = ptx_alloc<uint32_t>(bp, PTX_ADM_WT_WORDS);
             PTX_BAIL_CAPACITY();
-            PTX_LEADER { H->cur[7] = 0; }
-            PTX_SYNC_LDS();
             const uint32_t nwv_ = PTX_NWAVES;
             const uint32_t step = PTX_WS * PTX_AC; /* changes per wave and step */
-            const uint32_t seg = ((C + nwv_ - 1u) / nwv_ + step - 1u) / step * step; /* changes per wave, whole steps */
+            const uint32_t seg = ((C - adm_from + nwv_ - 1u) / nwv_ + step - 1u) / step * step; /* changes per wave, whole steps (of the changes behind the mark) */
             /* FAST CHECK, one pass: every wave walks its segment with clocks RELATIVE to the segment's start (the loads of the next
              * step in flight).  For every change of actor a,  seq (-) relative clock[a]  must be one and the same number G[a] (then
              * G[a] - 1 is the clock before the segment), and per actor b the maximum of  deps[b] (-) relative clock[b]  must not
              * exceed the clock before the segment ((-) saturates at 0).  The clocks before the segments are only known once every
              * wave has counted its own: the few per-wave numbers are validated after the pass.  A log that fails (rare) is walked
              * again by the exact two-pass code below, which names the first failing change. */
-            uint32_t* wrec = ptx_alloc<uint32_t>(bp, (PTX_MAX_THREADS / 64 + 1) * 12u);
+            uint32_t* wrec = ptx_alloc<uint32_t>(bp, PTX_ADM_WREC3_WORDS);
             PTX_BAIL_CAPACITY();
+            /* what the admitted prefix brings: its rows, and its clock — left in the spare record behind the waves' (nothing of the mark stays in a register
+             * across the walk); all zero for a walk from 0 */
+            uint32_t* const wrec0 = wrec + (PTX_MAX_THREADS / 64) * 12u;
+            PTX_LEADER {
+                H->cur[7] = adm_from ? mk[1] : 0u;
+                wrec0[0] = adm_from ? mk[2] : 0u;
+                wrec0[1] = adm_from ? mk[3] : 0u;
+            }
+            PTX_SYNC_LDS();
             PTX_FOR_WAVE(w, lane) {
-                const uint32_t lo = w * seg < C ? w * seg : C, hi = lo + seg < C ? lo + seg : C;
+                const uint32_t lo = adm_from + w * seg < C ? adm_from + w * seg : C, hi = lo + seg < C ? lo + seg : C;
                 /* Relative clocks of the wave's segment, packed like the envelope row they are compared with (u16 seq, deps[0..3)):
                  * cx = clock[0] << 16 (beside deps[0]; the half beside seq stays 0), cy = clock[1] | clock[2] << 16 (beside deps[1], deps[2]).
                  * Per change a handful of packed 16-bit operations: the own actor's clock through a byte permute, seq (-) clock and
@@ -1185,7 +1231,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             PTX_SYNC_LDS();
             bool admitted = H->cur[7] == N; /* the same answer in every thread: wrec is complete.  The changes must tile the rows of the log exactly */
             {
-                uint32_t B[3] = {0u, 0u, 0u};
+                uint32_t B[3] = {wrec0[0] & 0xFFFFu, wrec0[0] >> 16, wrec0[1]}; /* the clock before the first wave's segment */
                 for (uint32_t w = 0; w < nwv_; ++w) {
                     const uint32_t* r = wrec + w * 12u;
                     const uint32_t G[3] = {r[2] >> 16, r[3] & 0xFFFFu, r[3] >> 16}, M[3] = {r[6] >> 16, r[7] & 0xFFFFu, r[7] >> 16};
@@ -1199,10 +1245,19 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
                     B[1] += r[1] & 0xFFFFu;
                     B[2] += r[1] >> 16;
                 }
+                if (kMarks && admitted) { /* every change of the log is admitted: say so, once (a later launch finds x == C and comes nowhere near here) */
+                    ptx_adm_mark* const marks = PTX_FRESH_ARGS(A).adm_marks;
+                    if (marks) PTX_LEADER {
+                        const ptx_adm_mark done = {C, N, B[0] | (B[1] << 16), B[2]};
+                        marks[log] = done;
+                    }
+                }
             }
             if (!admitted) {
-                /* EXACT walk of a failing log: which change fails first, and how (the reference throws there) */
+                /* EXACT walk of a failing log: which change fails first, and how (the reference throws there).  Always from change 0 — the prefix behind a mark is
+                 * valid, so the first failing change is the same one */
                 PTX_NOTE_EXACT_WALK(); /* test / diagnostic hook: valid logs must never come here */
+                const uint32_t seg = ((C + nwv_ - 1u) / nwv_ + step - 1u) / step * step; /* (of the whole log) */
                 PTX_SYNC_LDS();
                 PTX_LEADER { H->cur[7] = 0; }
                 PTX_SYNC_LDS();
@@ -1320,7 +1375,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
              * (ptx_adm_step_n).  A log that passes is admitted; one that fails (rare) goes through the table below, which names the first failing change.
              * Two builds (kManyActors 1: up to seven actors, the walk over 16-byte rows; 2: eight to fifteen — its wider words would cost the first build
              * two waves per SIMD); documents of more than fifteen actors take the table of the first. */
-            uint32_t* wrec = ptx_alloc<uint32_t>(bp, (PTX_MAX_THREADS / 64 + 1) * PTX_ADMN_WREC);
+            uint32_t* wrec = ptx_alloc<uint32_t>(bp, PTX_ADM_WRECN_WORDS);
             PTX_BAIL_CAPACITY();
             if constexpr (kManyActors == 2) {
                 fast_admitted = na <= 11u ? ptx_adm_walk_n<6, 2, kThreads>(A, H, wrec, c_hdr, c_env, C, N, na) : ptx_adm_walk_n<8, 2, kThreads>(A, H, wrec, c_hdr, c_env, C, N, na);
@@ -1330,12 +1385,22 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             bp.off = (kDiag ? PTX_HDR_BYTES_DIAG : PTX_HDR_BYTES);
             if (!fast_admitted) PTX_NOTE_EXACT_WALK();
         }
+        /* the mark of a document of more than three actors says "all of it" or nothing (its clock does not fit the record: a grown log is walked from 0) */
+#define PTX_ADM_MARK_ALL()                                                    \
+    do {                                                                      \
+        ptx_adm_mark* const marks_ = kMarks ? A.adm_marks : nullptr;          \
+        if (marks_) PTX_LEADER {                                              \
+            const ptx_adm_mark done_ = {C, N, 0u, 0u};                        \
+            marks_[log] = done_;                                              \
+        }                                                                     \
+    } while (0)
+        if (fast_admitted) PTX_ADM_MARK_ALL();
         if (!fast_admitted) {
         /* More than fifteen actors, or a log that failed the check above (rare): tbl[first[a] + seq - 1] = index of the change (a, seq) makes "the seqs of an
          * actor are 1, 2, ... in log order" and "dependency (b, d) sits earlier in the log" one LDS read each.  Kept
          * deliberately plain (one change per thread and step, serial prefix by the leader). */
-        uint32_t* first = ptx_alloc<uint32_t>(bp, na + 2); /* changes per actor -> first table slot of the actor */
-        uint32_t* tbl = ptx_alloc<uint32_t>(bp, C + 1);     /* (actor, seq) -> index of the EARLIEST change that claims it (atomic minimum: which change a duplicate
+        uint32_t* first = ptx_alloc<uint32_t>(bp, PTX_ADM_FIRST_WORDS(na)); /* changes per actor -> first table slot of the actor */
+        uint32_t* tbl = ptx_alloc<uint32_t>(bp, PTX_ADM_TBL_WORDS(C)); /* (actor, seq) -> index of the EARLIEST change that claims it (atomic minimum: which change a duplicate
                                                                fails at must not depend on the order the threads run in; the reference throws at the later one) */
         PTX_BAIL_CAPACITY();
         PTX_FOR(a, na + 2) first[a] = 0;
@@ -1394,8 +1459,10 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         /* a failed admission stays pending in H->adm: an op-level error of an EARLIER row (found by the phases
          * below, which still run) wins over it, exactly as in a sequential replay */
         PTX_SYNC_LDS();
+        if (H->adm == PTX_NO_ERR) PTX_ADM_MARK_ALL(); /* (the same answer in every thread: the table's checks are behind the barrier) */
         bp.off = (kDiag ? PTX_HDR_BYTES_DIAG : PTX_HDR_BYTES);
         } /* the table */
+#undef PTX_ADM_MARK_ALL
         } /* na > 3 */
 #undef PTX_CHANGE_ROW
     }

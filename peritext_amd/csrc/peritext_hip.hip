@@ -688,6 +688,10 @@ struct ptx_dbatch {
     uint16_t* chg_env_hi = nullptr; /* the wide column (high halves of chg_env's values), only when some value of the batch needs it */
     uint32_t max_actors = 0;
     uint64_t n_changes = 0;
+    /* admission marks (merge_core.h ptx_adm_mark), one 16-byte record per log: what the merge kernel's P0 has admitted of the log so far.  Only a batch that owns
+     * its columns and carries the envelope has them (the columns of such a batch never change: what was admitted stays admitted); the one piece of a batch that
+     * a merge WRITES — zeroed when the batch is made, freed with it */
+    ptx_adm_mark* adm_marks = nullptr;
     /* launch shape derived from the largest log */
     uint32_t max_log_ops = 0;
     uint32_t lds_bytes = 0;
@@ -759,6 +763,11 @@ static void shape_launch(ptx_ctx* ctx, ptx_dbatch* b, uint64_t need, uint32_t ma
 /* Census of a resident batch: headers (computed on the device unless the caller supplied them) and the
  * launch shape.  `have_hdr`: b->log_hdr already holds the caller's headers. */
 static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr) {
+    if (b->owns && b->chg_off && b->n_logs && !b->adm_marks) { /* every batch the library makes comes through here once: nothing of it is admitted yet (an append has copied its base's marks before) */
+        hipError_t e = ptx_dev_malloc((void**)&b->adm_marks, (size_t)b->n_logs * sizeof(ptx_adm_mark));
+        if (e == hipSuccess) e = hipMemsetAsync(b->adm_marks, 0, (size_t)b->n_logs * sizeof(ptx_adm_mark), ctx->stream);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("admission marks: ") + hipGetErrorString(e));
+    }
     uint32_t *shape = nullptr, *d_need = nullptr;
     uint64_t* d_big = nullptr;
     uint32_t h[4] = {0, 0, 0, 0};
@@ -1064,6 +1073,7 @@ void ptx_batch_free(ptx_ctx* ctx, ptx_dbatch* b) {
     (void)ptx_dev_free(b->chg_hdr);
     (void)ptx_dev_free(b->chg_env);
     (void)ptx_dev_free(b->chg_env_hi);
+    (void)ptx_dev_free(b->adm_marks);
     delete b;
 }
 
@@ -1257,6 +1267,12 @@ ptx_status ptx_batch_append_device(ptx_ctx* ctx, const ptx_dbatch* base, const p
         if (env) PTX_TRYA(hipMemsetAsync(b->chg_off, 0, 8, ctx->stream));
         PTX_TRYA(hipStreamSynchronize(ctx->stream));
     }
+    /* what the base's merges have admitted of every log stays admitted: the new log is the old one and more.  (A record holds the clock of up to three actors;
+     * a batch of more starts from nothing, as does one whose base has no marks) */
+    if (env && L && base_env && base->adm_marks && base->max_actors <= 3u && b->max_actors <= 3u) {
+        PTX_TRYA(ptx_dev_malloc((void**)&b->adm_marks, (size_t)L * sizeof(ptx_adm_mark)));
+        PTX_TRYA(hipMemcpyAsync(b->adm_marks, base->adm_marks, (size_t)L * sizeof(ptx_adm_mark), hipMemcpyDeviceToDevice, ctx->stream));
+    }
 #undef PTX_TRYA
     (void)ptx_dev_free(zero_off);
     const ptx_status st = census_and_shape(ctx, b, false);
@@ -1388,6 +1404,8 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
     A.big_scratch = b->big_scratch;
     A.big_off = b->big_off;
     A.grid_bar = nullptr;
+    /* (the diagnostic launches measure the walk; PTX_FLAG_READMIT asks for it) */
+    A.adm_marks = admit && !(ctx->flags & PTX_FLAG_READMIT) && !ctx->clocks && !ctx->stop_after ? b->adm_marks : nullptr;
     /* one workgroup per log; far more workgroups than the 256 CUs so the dispatcher load-balances.  Up to three launches (census_and_shape): the many at
      * their LDS window, the few that need a larger one, the logs beyond one CU's LDS through the HBM-staged kernel — the latter two on a side stream forked
      * from and joined to the caller's, so that they run beside the many instead of after them. */

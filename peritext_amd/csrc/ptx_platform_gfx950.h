@@ -308,6 +308,13 @@ PTX_DEV const ArgsT& ptx_fresh_args(const ArgsT&) {
 #define PTX_FRESH_ARGS(A) ptx_fresh_args(A)
 /* a word of the batch that no kernel of the call writes (offsets, headers), at an address that is the same in every lane: read through the constant address space,
  * i.e. by the scalar unit (left to itself the compiler only does so where it can prove that no store of the kernel so far may alias the word) */
+/* ONE exception to "no kernel of the call writes it": a log's admission mark (merge_core.h ptx_adm_mark), which the log's OWN workgroup may store once, after and
+ * depending on this load (no reload is ever made, so nothing can be moved over the store), and which a launch on another stream may store meanwhile.  What such a
+ * reader gets — the scalar cache's line, the old record, the new one, or (should a 16-byte scalar load against a 16-byte vector store ever tear) words of both —
+ * is safe word by word, not by atomicity: both records are true of the same immutable log; {new changes, new rows, any clock} skips a walk that has passed;
+ * {old changes, old rows, new clock} starts the suffix walk from a clock that disagrees with the seq of the first appended change of every actor that has one,
+ * {old changes, new rows} breaks the rows-tile-the-log sum: either way the one-pass check fails and the exact walk from change 0 decides, as without marks.
+ * A vector load here would make the record lane-variant to the compiler and P0's skip / suffix choice a vector branch in every build. */
 template <class T>
 PTX_DEV T ptx_const_load(const T* p) { return *(const __attribute__((address_space(4))) T*)p; }
 #define PTX_CONST_LOAD(p) ptx_const_load(p)
