@@ -321,6 +321,7 @@ void ptx_batch_free(ptx_ctx* ctx, ptx_dbatch* b);
 uint32_t ptx_batch_n_logs(const ptx_dbatch* b);
 uint64_t ptx_batch_n_ops(const ptx_dbatch* b);
 uint64_t ptx_batch_n_changes(const ptx_dbatch* b); /* rows of the Change envelope (0 = the batch has none) */
+uint32_t ptx_batch_max_actors(const ptx_dbatch* b); /* actor ranks per envelope row: the width of a ptx_batch_at_versions clock (0 = the batch has no envelope) */
 /* Launch shape the library derived from the batch's log headers: threads per workgroup (= per log) and
  * dynamic LDS bytes per workgroup (the largest log's working set; it sets how many logs share a CU).  When at most a
  * tenth of the logs need more LDS than would let one more log share a CU, those are merged in a second launch of
@@ -598,6 +599,29 @@ ptx_status ptx_batch_append_device(ptx_ctx* ctx, const ptx_dbatch* base, const p
  * logs below the batch format's own; the per-actor tables (24 bytes per actor) must fit one CU's LDS.  The call synchronises. */
 ptx_status ptx_sync_replicas(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_pairs, const uint32_t* src_log, const uint32_t* dst_log, uint32_t max_attempts,
                              ptx_dbatch** more, uint32_t* status_out);
+
+/* ---- documents at a past version: resident logs cut at vector clocks or at a prefix of their own history, the logs staying resident ----
+ * Cut c reads the source log src_log[c] (HOST array) of `base`, a batch with the Change envelope; the actor ranks are the batch's own.  Per call either
+ *   clock cuts    clocks[c * max_actors + a] (HOST, u32): a change of actor a is KEPT iff seq <= clocks[c][a] — micromerge.ts:511 sets clock[actor] = seq at every
+ *                 admission, so that is the set a replica with this clock holds.  0 keeps none of the actor, PTX_VERSION_ALL all; exact lo | hi << 16 where the
+ *                 batch has chg_env_hi.  A clock no replica could have had — a kept change with a non-zero deps[b], b not its own actor, > clocks[c][b] — is that
+ *                 cut's PTX_ERR_MISSING_DEP: applyChange throws "Missing dependency" (micromerge.ts:505-508) at that change on a fresh Micromerge.  Checked on the
+ *                 envelope alone; the source log is not re-admitted (an inadmissible source shows at the cut log's merge, as a grown log does after a sync), or
+ *   prefix cuts   prefix[c] = k (HOST) keeps the first min(k, n) changes: the version the replica itself was at after its k-th applyChange / change().
+ * Both or neither given is PTX_ERR_INVALID_ARG, as are src_log[c] >= n_logs and a batch without the envelope.
+ * *out = a resident batch of n_cuts logs, base's max_actors, the wide column iff `base` has one, computed headers and launch shape: log c = the kept changes of
+ * cut c IN LOG ORDER with their op rows, chg_hdr and envelope rows (admissible in that order for a closed clock: every dep of a kept change stands before it
+ * and is kept).  With PTX_VERSIONS_THEN_REST the dropped changes follow the kept ones, also in log order — a stable partition that merges to the source's
+ * present document — and first_row_out[c] is what ptx_replay_patches_from takes as first_row: the stream it returns is the Patch[] from version V to the present.
+ * Per cut (caller memory, [n_cuts]; each may be NULL except status_out): status_out PTX_OK, PTX_ERR_MISSING_DEP, PTX_ERR_CAPACITY (a narrow envelope with a
+ * saturated value, 65 535, in the source log) or PTX_ERR_BAD_OP (an actor rank >= max_actors); n_kept_out the changes kept; first_row_out their op rows;
+ * clocks_out[c * max_actors + a] the largest kept seq of actor a, 0 = none (how a caller of a prefix cut learns the version's clock).  A failed cut
+ * contributes an EMPTY log and zero outputs; `base` is never touched.  A log may be the source of any number of cuts; n_cuts == 0 is an empty batch.  The call
+ * synchronises. */
+#define PTX_VERSION_ALL 0xFFFFFFFFu
+#define PTX_VERSIONS_THEN_REST 1u
+ptx_status ptx_batch_at_versions(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_cuts, const uint32_t* src_log, const uint32_t* clocks, const uint32_t* prefix,
+                                 uint32_t flags, ptx_dbatch** out, uint32_t* status_out, uint32_t* n_kept_out, uint32_t* first_row_out, uint32_t* clocks_out);
 
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {

@@ -45,6 +45,8 @@ ERR_CAPACITY = 5
 ERR_BAD_OP = 6
 ERR_INDEX_OOB = 7
 ERR_SYNC_NOT_CONVERGED = 8  # per pair (ptx_sync_replicas): "applyChanges did not converge", reference/test/merge.ts:18-19
+VERSION_ALL = 0xFFFFFFFF  # ptx_batch_at_versions: a clock entry that keeps every change of the actor
+VERSIONS_THEN_REST = 1  # ... flag: the dropped changes follow the kept ones
 ERR_INVALID_ARG = 100
 ERR_HIP = 101
 ERR_NO_DEVICE = 102
@@ -336,6 +338,8 @@ FUNCTIONS = {
     "ptx_change": (C.c_int32, [vp, vp, vp, C.POINTER(ptx_input_ops), C.POINTER(vp), u32p]),
     "ptx_batch_append_device": (C.c_int32, [vp, vp, vp, C.POINTER(vp)]),
     "ptx_sync_replicas": (C.c_int32, [vp, vp, C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(vp), u32p]),
+    "ptx_batch_at_versions": (C.c_int32, [vp, vp, C.c_uint32, u32p, u32p, u32p, C.c_uint32, C.POINTER(vp), u32p, u32p, u32p, u32p]),
+    "ptx_batch_max_actors": (C.c_uint32, [vp]),
     "ptx_batch_download": (C.c_int32, [vp, vp, C.POINTER(ptx_host_batch)]),
     "ptx_host_batch_free": (None, [C.POINTER(ptx_host_batch)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),

@@ -34,6 +34,7 @@
 #include "cursor_core.h"
 #include "rootmap_core.h"
 #include "sync_core.h"
+#include "version_core.h"
 #include "accum_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -199,6 +200,11 @@ extern "C" __global__ void __launch_bounds__(64) ptx_sync_plan_kernel(PtxSyncArg
 }
 extern "C" __global__ void __launch_bounds__(PTX_SYNC_GATHER_THREADS) ptx_sync_gather_kernel(PtxSyncArgs A, PtxSyncGatherArgs G) {
     if (blockIdx.x < A.n_pairs) ptx_sync_gather_pair<PTX_SYNC_GATHER_THREADS>(A, G, blockIdx.x);
+}
+/* a resident log at a past version (version_core.h): one wave per cut plans (the kept changes, the rest behind them); ptx_sync_gather_kernel copies */
+extern "C" __global__ void __launch_bounds__(64) ptx_version_plan_kernel(PtxVersionArgs V) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
+    if (blockIdx.x < V.S.n_pairs) ptx_version_plan_cut<64>(V, blockIdx.x, ptx_lds);
 }
 
 /* patch streams back into canonical rows (accum_core.h): one wave per log, the state in the log's LDS window or — a log beyond one CU's LDS, or
@@ -1084,6 +1090,7 @@ void ptx_batch_launch_shape(const ptx_dbatch* b, uint32_t* threads, uint32_t* ld
 }
 uint64_t ptx_batch_n_ops(const ptx_dbatch* b) { return b ? b->n_ops : 0; }
 uint64_t ptx_batch_n_changes(const ptx_dbatch* b) { return b && b->chg_off ? b->n_changes : 0; }
+uint32_t ptx_batch_max_actors(const ptx_dbatch* b) { return b && b->chg_off ? b->max_actors : 0; }
 
 ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t copies, ptx_dbatch** out) {
     if (!ctx || !out) return PTX_ERR_INVALID_ARG;
@@ -3276,6 +3283,160 @@ ptx_status ptx_sync_replicas(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_pa
         return st;
     }
     *more = b;
+    return PTX_OK;
+}
+
+/* ---- resident logs at a past version: the kept changes of every cut, optionally the rest behind them (version_core.h) ---- */
+ptx_status ptx_batch_at_versions(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_cuts, const uint32_t* src_log, const uint32_t* clocks, const uint32_t* prefix, uint32_t flags,
+                                 ptx_dbatch** out, uint32_t* status_out, uint32_t* n_kept_out, uint32_t* first_row_out, uint32_t* clocks_out) {
+    if (!ctx || !base || !out || (n_cuts && (!src_log || !status_out))) return PTX_ERR_INVALID_ARG;
+    *out = nullptr;
+    const uint32_t L = base->n_logs, P = n_cuts, na = base->max_actors;
+    if (!base->chg_off || !base->chg_hdr || !base->chg_env || na == 0) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_batch_at_versions needs the Change envelope of the batch (the changes' seqs and deps)");
+    if (P && (clocks != nullptr) == (prefix != nullptr)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_batch_at_versions takes clock cuts or prefix cuts, one of the two");
+    if (flags & ~PTX_VERSIONS_THEN_REST) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_batch_at_versions: unknown flag");
+    for (uint32_t c = 0; c < P; ++c)
+        if (src_log[c] >= L) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_batch_at_versions: a cut names a log the batch does not have");
+    const uint64_t lds_need = (ptx_version_lds_need(na) + 255) & ~255ull;
+    if (lds_need > ctx->max_lds) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_batch_at_versions: the per-actor clocks of max_actors do not fit one CU's LDS");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    auto staging = [&](size_t bytes) -> hipError_t { /* the pinned staging block of the context's small uploads, grown on demand */
+        if (ctx->up_h_cap >= bytes) return hipSuccess;
+        if (ctx->up_h) (void)hipHostFree(ctx->up_h);
+        ctx->up_h = nullptr;
+        ctx->up_h_cap = 0;
+        hipError_t e = hipHostMalloc((void**)&ctx->up_h, 2 * bytes, hipHostMallocDefault);
+        if (e == hipSuccess) ctx->up_h_cap = 2 * bytes;
+        return e;
+    };
+    uint8_t* d_in = nullptr;
+    uint32_t *d_scratch = nullptr, *d_out = nullptr;
+    ptx_dbatch* b = nullptr;
+    auto drop = [&]() {
+        (void)ptx_dev_free(d_in);
+        (void)ptx_dev_free(d_scratch);
+        (void)ptx_dev_free(d_out);
+        d_in = nullptr;
+        d_scratch = d_out = nullptr;
+    };
+#define PTX_TRYV(call)                                  \
+    do {                                                \
+        hipError_t _e = (call);                         \
+        if (_e != hipSuccess) {                         \
+            std::string msg = std::string(#call) + ": " + hipGetErrorString(_e); \
+            drop();                                     \
+            ptx_batch_free(ctx, b);                     \
+            return fail(ctx, _e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, msg); \
+        }                                               \
+    } while (0)
+    /* the envelope offsets of the base size the scratch slices: one small copy through the pinned block */
+    const size_t off_bytes = ((size_t)L + 1) * 8, cut_bytes = ((size_t)P * 4 + 15) & ~(size_t)15, scr_bytes = ((size_t)P + 1) * 8;
+    const size_t want_bytes = clocks ? (size_t)P * na * 4 : (size_t)P * 4;
+    const size_t in_bytes = 2 * cut_bytes + scr_bytes + want_bytes;  /* src_log | dst_log | scr_off | clocks or prefix */
+    const size_t out_words = (5 + (size_t)na) * P;                   /* status | changes | rows | n_kept | first_row | clocks_out */
+    PTX_TRYV(staging(std::max(off_bytes, std::max(in_bytes, out_words * 4))));
+    PTX_TRYV(hipMemcpyAsync(ctx->up_h, base->chg_off, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PTX_TRYV(hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> scr((size_t)P + 1, 0);
+    {
+        const uint64_t* coff = (const uint64_t*)ctx->up_h;
+        for (uint32_t c = 0; c < P; ++c) scr[c + 1] = scr[c] + ptx_sync_scratch_words(coff[src_log[c] + 1] - coff[src_log[c]]);
+    }
+    std::vector<uint32_t> outw(out_words + 1, 0);
+    PtxVersionArgs V;
+    memset(&V, 0, sizeof(V));
+    PtxSyncArgs& A = V.S;
+    if (P) {
+        PTX_TRYV(ptx_dev_malloc((void**)&d_in, in_bytes));
+        PTX_TRYV(dalloc(&d_scratch, scr[P]));
+        PTX_TRYV(dalloc(&d_out, (uint64_t)out_words));
+        memcpy(ctx->up_h, src_log, (size_t)P * 4);
+        for (uint32_t c = 0; c < P; ++c) ((uint32_t*)(ctx->up_h + cut_bytes))[c] = c; /* log c of *out is cut c */
+        memcpy(ctx->up_h + 2 * cut_bytes, scr.data(), scr_bytes);
+        memcpy(ctx->up_h + 2 * cut_bytes + scr_bytes, clocks ? clocks : prefix, want_bytes);
+        PTX_TRYV(hipMemcpyAsync(d_in, ctx->up_h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    A.log_off = base->log_off;
+    A.chg_off = base->chg_off;
+    A.chg_hdr = base->chg_hdr;
+    A.chg_env = base->chg_env;
+    A.chg_env_hi = base->chg_env_hi;
+    A.max_actors = na;
+    A.n_pairs = P;
+    A.src_log = (const uint32_t*)d_in;
+    A.dst_log = (const uint32_t*)(d_in + cut_bytes);
+    A.scr_off = (const uint64_t*)(d_in + 2 * cut_bytes);
+    A.scratch = d_scratch;
+    A.status = d_out;
+    A.n_admitted = d_out + P;
+    A.n_rows = d_out + 2 * (size_t)P;
+    A.lds_bytes = (uint32_t)lds_need;
+    V.clocks = clocks ? (const uint32_t*)(d_in + 2 * cut_bytes + scr_bytes) : nullptr;
+    V.prefix = clocks ? nullptr : (const uint32_t*)(d_in + 2 * cut_bytes + scr_bytes);
+    V.flags = flags;
+    V.n_kept = d_out + 3 * (size_t)P;
+    V.first_row = d_out + 4 * (size_t)P;
+    V.clocks_out = d_out + 5 * (size_t)P;
+    if (P) {
+        hipLaunchKernelGGL(ptx_version_plan_kernel, dim3(P), dim3(64), (uint32_t)lds_need, ctx->stream, V);
+        PTX_TRYV(hipGetLastError());
+        /* one copy back: the totals and the effective clock of every cut */
+        PTX_TRYV(hipMemcpyAsync(ctx->up_h, d_out, out_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYV(hipStreamSynchronize(ctx->stream));
+        memcpy(outw.data(), ctx->up_h, out_words * 4);
+        memcpy(status_out, outw.data(), (size_t)P * 4);
+        if (n_kept_out) memcpy(n_kept_out, outw.data() + 3 * (size_t)P, (size_t)P * 4);
+        if (first_row_out) memcpy(first_row_out, outw.data() + 4 * (size_t)P, (size_t)P * 4);
+        if (clocks_out) memcpy(clocks_out, outw.data() + 5 * (size_t)P, (size_t)P * na * 4);
+    }
+    /* *out: log c = cut c */
+    std::vector<uint64_t> doff((size_t)P + 1, 0), dcoff((size_t)P + 1, 0);
+    for (uint32_t c = 0; c < P; ++c) {
+        dcoff[c + 1] = dcoff[c] + outw[(size_t)P + c];
+        doff[c + 1] = doff[c] + outw[2 * (size_t)P + c];
+    }
+    b = new ptx_dbatch();
+    b->n_logs = P;
+    b->n_ops = doff[P];
+    b->max_actors = na;
+    b->n_changes = dcoff[P];
+    const uint64_t ES = PTX_ENV_STRIDE(na);
+    const size_t poff_bytes = ((size_t)P + 1) * 8;
+    PTX_TRYV(dalloc(&b->log_off, (uint64_t)P + 1));
+    PTX_TRYV(dalloc(&b->chg_off, (uint64_t)P + 1));
+    PTX_TRYV(staging(2 * poff_bytes));
+    memcpy(ctx->up_h, doff.data(), poff_bytes);
+    memcpy(ctx->up_h + poff_bytes, dcoff.data(), poff_bytes);
+    PTX_TRYV(hipMemcpyAsync(b->log_off, ctx->up_h, poff_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PTX_TRYV(hipMemcpyAsync(b->chg_off, ctx->up_h + poff_bytes, poff_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PTX_TRYV(dalloc(&b->op_id, b->n_ops));
+    PTX_TRYV(dalloc(&b->ref_a, b->n_ops));
+    PTX_TRYV(dalloc(&b->ref_b, b->n_ops));
+    PTX_TRYV(dalloc(&b->payload, b->n_ops));
+    PTX_TRYV(dalloc(&b->action, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYV(dalloc(&b->mark_type, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYV(dalloc(&b->side_a, b->n_ops));
+    PTX_TRYV(dalloc(&b->side_b, b->n_ops));
+    PTX_TRYV(dalloc(&b->log_hdr, (uint64_t)P));
+    PTX_TRYV(dalloc(&b->chg_hdr, b->n_changes + PTX_ENV_PAD));
+    PTX_TRYV(dalloc(&b->chg_env, (b->n_changes + PTX_ENV_PAD) * ES));
+    if (base->chg_env_hi) PTX_TRYV(dalloc(&b->chg_env_hi, (b->n_changes + PTX_ENV_PAD) * ES));
+    if (P && b->n_changes) {
+        PtxSyncGatherArgs G = {base->op_id, base->ref_a, base->ref_b, base->payload, base->action, base->mark_type, base->side_a, base->side_b,
+                               b->op_id, b->ref_a, b->ref_b, b->payload, b->action, b->mark_type, b->side_a, b->side_b,
+                               b->chg_hdr, b->chg_env, b->chg_env_hi, b->log_off, b->chg_off};
+        hipLaunchKernelGGL(ptx_sync_gather_kernel, dim3(P), dim3(PTX_SYNC_GATHER_THREADS), 0, ctx->stream, A, G);
+        PTX_TRYV(hipGetLastError());
+    }
+    PTX_TRYV(hipStreamSynchronize(ctx->stream));
+#undef PTX_TRYV
+    drop();
+    const ptx_status st = census_and_shape(ctx, b, false);
+    if (st != PTX_OK) {
+        ptx_batch_free(ctx, b);
+        return st;
+    }
+    *out = b;
     return PTX_OK;
 }
 

@@ -186,6 +186,31 @@ class Engine:
                                                status.ctypes.data_as(abi.u32p)))
         return h, status[:n]
 
+    def at_versions(self, dbatch, cuts, clocks=None, prefix=None, then_rest=False):
+        """Resident logs at a past version (ptx_batch_at_versions): `cuts` = the source log of every cut; either `clocks` ([n_cuts, max_actors] u32: a change of
+        actor a is kept iff seq <= clocks[c][a], abi.VERSION_ALL = all) or `prefix` ([n_cuts]: the first k changes of the log).  then_rest: the dropped
+        changes follow the kept ones, and first_row[c] is what replay_patches takes as first_row for the Patch[] from that version to the present.
+        Returns (resident batch whose log c is cut c, status, n_kept, first_row, clocks_out [n_cuts, max_actors]) — the last four numpy arrays; a failed
+        cut (abi.ERR_MISSING_DEP for a clock no replica could have had, ERR_CAPACITY, ERR_BAD_OP) is an empty log."""
+        src = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+        n, na = len(src), int(self.lib.ptx_batch_max_actors(dbatch))
+        ck = pf = None
+        if clocks is not None:
+            ck = np.ascontiguousarray(clocks, dtype=np.uint32).reshape(-1)
+            if len(ck) != n * na:
+                raise ValueError("at_versions: clocks must hold max_actors (%d) entries per cut" % na)
+        if prefix is not None:
+            pf = np.ascontiguousarray(prefix, dtype=np.uint32).reshape(-1)
+            if len(pf) != n:
+                raise ValueError("at_versions: prefix must hold one entry per cut")
+        ptr = lambda a: a.ctypes.data_as(abi.u32p) if a is not None and len(a) else (C.cast(C.c_void_p(a.ctypes.data), abi.u32p) if a is not None else None)  # noqa: E731
+        status, n_kept, first_row = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        clocks_out = np.zeros(max(n * na, 1), dtype=np.uint32)
+        h = C.c_void_p()
+        self._check(self.lib.ptx_batch_at_versions(self.ctx, dbatch, n, ptr(src), ptr(ck), ptr(pf), abi.VERSIONS_THEN_REST if then_rest else 0, C.byref(h), ptr(status),
+                                                   ptr(n_kept), ptr(first_row), ptr(clocks_out)))
+        return h, status[:n], n_kept[:n], first_row[:n], clocks_out[: n * na].reshape(n, na)
+
     def free_batch(self, h):
         self.lib.ptx_batch_free(self.ctx, h)
 

@@ -63,6 +63,9 @@ struct Lib {
     ptx_status (*batch_append_device)(ptx_ctx*, const ptx_dbatch*, const ptx_dbatch*, ptx_dbatch**) = nullptr;
     /* sync of replica logs: getMissingChanges + applyChanges */
     ptx_status (*sync_replicas)(ptx_ctx*, const ptx_dbatch*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, ptx_dbatch**, uint32_t*) = nullptr;
+    /* resident logs at a past version: clock cuts and prefix cuts */
+    ptx_status (*batch_at_versions)(ptx_ctx*, const ptx_dbatch*, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, ptx_dbatch**, uint32_t*, uint32_t*, uint32_t*,
+                                    uint32_t*) = nullptr;
     /* multi-GPU: the digest all-gather (RCCL inside the library) */
     ptx_status (*comm_unique_id)(ptx_ctx*, uint8_t*) = nullptr;
     ptx_status (*comm_init)(ptx_ctx*, const uint8_t*, uint32_t, uint32_t, ptx_comm**) = nullptr;
@@ -128,7 +131,8 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.allgather_digests, "ptx_allgather_digests") && sym(L.count_converged_digests, "ptx_count_converged_digests") &&
                   sym(L.result_download_logs, "ptx_result_download_logs") && sym(L.root_map, "ptx_root_map") && sym(L.root_maps_free, "ptx_root_maps_free") && sym(L.device_alloc, "ptx_device_alloc") && sym(L.device_free, "ptx_device_free") &&
                   sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device") &&
-                  sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches");
+                  sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches") &&
+                  sym(L.batch_at_versions, "ptx_batch_at_versions");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -752,6 +756,73 @@ napi_value SyncReplicas(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* batchAtVersions(ctx, batch, {src: Uint32Array, clocks | prefix: Uint32Array, thenRest, diff}): the replica logs of `batch` at past versions
+ * (ptx_batch_at_versions).  Cut c reads log src[c]; clocks holds maxActors entries per cut (0xFFFFFFFF = every change of the actor), prefix one.  Upload, cut,
+ * merge of the cut logs and — diff — ptx_replay_patches_from at the kept rows (thenRest is implied: the stream from the version to the present).  Returns
+ * {batch: WireBatch columns of the cut logs, status, nKept, firstRow, clocksOut: Uint32Arrays, result: the result object of applyMaterialize for the cut logs}. */
+napi_value BatchAtVersions(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    if (!ctx) return throw_msg(env, "batchAtVersions(ctx, batch, {src, clocks | prefix, thenRest, diff})");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    const void *src = nullptr, *clocks = nullptr, *prefix = nullptr;
+    size_t n = 0, n_clocks = 0, n_prefix = 0;
+    if (!column(env, argv[2], "src", 4, &src, &n) || n > 0xFFFFFFFFull) return throw_msg(env, "batchAtVersions: src must be a Uint32Array");
+    if (!column(env, argv[2], "clocks", 4, &clocks, &n_clocks, true) || !column(env, argv[2], "prefix", 4, &prefix, &n_prefix, true))
+        return throw_msg(env, "batchAtVersions: clocks / prefix must be Uint32Arrays");
+    const size_t na = pb.max_actors;
+    if ((clocks && n_clocks != n * na) || (prefix && n_prefix != n)) return throw_msg(env, "batchAtVersions: clocks holds maxActors entries per cut, prefix one");
+    const bool diff = u32_prop(env, argv[2], "diff", 0u) != 0u, then_rest = diff || u32_prop(env, argv[2], "thenRest", 0u) != 0u;
+    std::vector<uint32_t> out((5 + na) * n + 1, 0); /* status | nKept | firstRow | clocksOut */
+    uint32_t none = 0; /* (a zero-length ArrayBuffer may come without storage) */
+    ptx_dbatch *db = nullptr, *cut = nullptr;
+    ptx_dresult* dr = nullptr;
+    ptx_host_batch hb;
+    ptx_result res;
+    ptx_patches pat;
+    memset(&hb, 0, sizeof(hb));
+    memset(&pat, 0, sizeof(pat));
+    bool have_res = false;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK)
+        st = L.batch_at_versions(ctx, db, (uint32_t)n, n ? (const uint32_t*)src : &none, (const uint32_t*)clocks, (const uint32_t*)prefix, then_rest ? PTX_VERSIONS_THEN_REST : 0u, &cut,
+                                 out.data(), out.data() + n, out.data() + 2 * n, out.data() + 3 * n);
+    if (st == PTX_OK) st = L.batch_download(ctx, cut, &hb);
+    if (st == PTX_OK) st = L.result_alloc(ctx, cut, &dr);
+    if (st == PTX_OK) st = L.merge(ctx, cut, dr);
+    if (st == PTX_OK) st = L.sync(ctx);
+    if (st == PTX_OK) st = L.result_download(ctx, cut, dr, &res);
+    have_res = st == PTX_OK;
+    if (st == PTX_OK && diff) st = L.replay_patches_from(ctx, cut, dr, out.data() + 2 * n, &pat);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (dr) L.dresult_free(ctx, dr);
+    if (cut) L.batch_free(ctx, cut);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) {
+        if (have_res) L.result_free(&res);
+        if (hb.owner) L.host_batch_free(&hb);
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "ptx_batch_at_versions failed (status %d): %s", st, err.c_str());
+        return throw_msg(env, msg);
+    }
+    napi_value o, v, batch = batch_to_js(env, hb.b);
+    L.host_batch_free(&hb);
+    napi_value result = result_to_js(env, res, diff ? &pat : nullptr);
+    if (!batch || !result || napi_create_object(env, &o) != napi_ok) return throw_msg(env, "batchAtVersions: cannot build the result object");
+    napi_set_named_property(env, o, "batch", batch);
+    napi_set_named_property(env, o, "result", result);
+    const char* names[4] = {"status", "nKept", "firstRow", "clocksOut"};
+    for (int k = 0; k < 4; ++k) {
+        v = make_u32(env, out.data() + (size_t)k * n, k < 3 ? n : n * na);
+        if (v) napi_set_named_property(env, o, names[k], v);
+    }
+    return o;
+}
+
 /* rootMap(ctx, batch): Micromerge.getRoot() for every replica log of the batch (ptx_root_map): upload, resolve.  Returns
  * {entryOff: BigUint64Array [n_logs + 1], logs: Uint32Array (status, n_entries, first_bad_row, 0 per log), entries: Uint32Array
  * (obj lo, obj hi, key, row, kind, value per entry)}. */
@@ -1036,7 +1107,8 @@ napi_value Init(napi_env env, napi_value exports) {
      * (non-enumerable) properties: index.js calls them by name */
     const napi_property_descriptor later[] = {{"syncReplicas", nullptr, SyncReplicas, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"accumulatePatches", nullptr, AccumulatePatches, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"checkPatches", nullptr, CheckPatches, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"checkPatches", nullptr, CheckPatches, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"batchAtVersions", nullptr, BatchAtVersions, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

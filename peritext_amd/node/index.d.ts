@@ -143,6 +143,9 @@ export class MergeEngine {
     changeMany(docs: Change[][][], calls: InputOperation[][][][], actors: ActorId[][], opts?: { extraComments?: string[][] }): { changes: Change[][][]; status: number[][] }
     /** getMissingChanges + applyChanges (test/merge.ts:4-38) for many replica pairs in one call (ptx_sync_replicas): per pair what `to` lacks, in the order it admits it */
     syncMany(docs: Change[][][], pairs: Array<{ doc: number; from: number; to: number }>, opts?: { maxAttempts?: number }): { changes: Change[][]; status: number[] }
+    /** documents at past versions, many cuts in one call (ptx_batch_at_versions): per cut the spans at the version, its effective clock and — opts.diff — the Patch[] from there to the replica's present;
+     *  a clock no replica could have had is status 3 with spans null */
+    documentsAt(docs: Change[][][], cuts: Array<{ doc: number; replica: number; clock: Record<ActorId, number> }> | Array<{ doc: number; replica: number; changes: number }>, opts?: { diff?: boolean }): Array<{ status: number; clock: Record<ActorId, number>; spans: FormatSpanWithText[] | null; patches?: Patch[] | null }>
     replica(docId?: number | string, actorId?: ActorId): ReplicaHandle
     flush(wantPatches?: boolean): void
 }
@@ -157,3 +160,5 @@ export function decodeRoot(batch: WireBatch, rm: WireRootMaps, log: number): Roo
 /** bridge.ts:394-414 prosemirrorDocFromCRDT, as the Node.toJSON() form of the document (parity unpinned: no ProseMirror in the build image) */
 export function prosemirrorDocFromSpans(spans: FormatSpanWithText[]): { type: "doc"; content: Array<{ type: "paragraph"; content?: Array<{ type: "text"; text: string; marks?: Array<{ type: MarkType; attrs?: Record<string, string> }> }> }> }
 export function census(batch: WireBatch): Uint32Array
+/** PTX_VERSION_ALL: a clock entry of documentsAt that keeps every change of the actor */
+export const VERSION_ALL: number

@@ -39,6 +39,7 @@ const STATUS_MESSAGES = {
 const IN = { INSERT: 0, DELETE: 1, ADDMARK: 2, REMOVEMARK: 3, MAKELIST: 4, MAPSET: 5, MAPDEL: 6 }
 const IN_OBJ_NEW = 0x80000000 /* ptx_input_ops.index of a map op: the object made by row k of this log's output */ /* ptx_input_ops.action */
 const CHG_ACTOR_SHIFT = 20, CHG_NOPS = 0x000fffff, ENV_SATURATED = 65535
+const VERSION_ALL = 0xffffffff /* PTX_VERSION_ALL: a clock entry that keeps every change of the actor */
 const envStride = maxActors => (1 + maxActors + 3) & ~3 /* PTX_ENV_STRIDE */
 
 /** chgActor / chgSeq / chgNops / chgDeps -> the packed envelope the device reads: chgHdr = actor << 20 | nops, chgEnv rows of
@@ -925,6 +926,56 @@ class MergeEngine {
         return { changes, status: Array.from(raw.status) }
     }
     /**
+     * Documents at a past version, many cuts in ONE call (ptx_batch_at_versions): docs = the replica logs applied so far (Change[][][]), cuts =
+     * [{doc, replica, clock: {actorId: seq}}] — the changes of actor a with seq <= clock[a], an absent actor is 0, VERSION_ALL keeps all of an actor — or
+     * [{doc, replica, changes: k}] — the first k changes of the log (the version the replica itself was at after its k-th applyChange); one kind per call.
+     * Returns per cut {status, clock: the version's effective clock, spans: getTextWithFormatting at that version (null for a failed cut and for a version
+     * without the text list)}; with opts.diff also `patches`: the Patch[] that takes the version to the replica's present (the cut, the merge and
+     * ptx_replay_patches_from all run on the device; a second call whose logs are the kept changes followed by the rest).  A clock no replica could have had is status 3 (STATUS_MESSAGES: the reference's "Missing
+     * dependency"): a failed cut is an empty log.
+     */
+    documentsAt(docs, cuts, opts) {
+        const byClock = cuts.length > 0 && cuts[0].clock !== undefined
+        if (cuts.some(c => (c.clock !== undefined) !== byClock || (c.changes !== undefined) === byClock)) throw new TypeError("documentsAt: every cut carries `clock`, or every cut carries `changes`")
+        const batch = encodeDocs(docs)
+        const first = []
+        let n = 0
+        docs.forEach(logs => {
+            first.push(n)
+            n += logs.length
+        })
+        for (const c of cuts) if (!(c.doc >= 0 && c.doc < docs.length && c.replica >= 0 && c.replica < docs[c.doc].length)) throw new RangeError("documentsAt: no replica " + c.replica + " of document " + c.doc)
+        const src = Uint32Array.from(cuts, c => first[c.doc] + c.replica)
+        const na = batch.maxActors, diff = !!(opts && opts.diff)
+        const arg = { src }
+        if (byClock) {
+            arg.clocks = new Uint32Array(cuts.length * na)
+            cuts.forEach((c, k) => {
+                const actors = batch.docActors[c.doc]
+                for (const a of Object.keys(c.clock)) {
+                    const rank = actors.indexOf(a)
+                    if (rank >= 0) arg.clocks[k * na + rank] = c.clock[a] >= VERSION_ALL ? VERSION_ALL : c.clock[a] /* (an actor the document never saw has no changes to keep) */
+                }
+            })
+        } else arg.prefix = Uint32Array.from(cuts, c => Math.min(c.changes, VERSION_ALL))
+        const tables = { values: batch.values, urls: batch.urls, logDoc: Array.from(src, l => batch.logDoc[l]), docActors: batch.docActors, docComments: batch.docComments, keys: batch.keys, mapValues: batch.mapValues }
+        const raw = this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 0 }, arg))
+        const cut = unpackEnvelope(Object.assign(raw.batch, tables))
+        /* diff: a second call whose logs are the kept changes followed by the rest, replayed from the kept rows on */
+        const rawDiff = diff ? this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 1 }, arg)) : null
+        const whole = diff ? unpackEnvelope(Object.assign(rawDiff.batch, tables)) : null
+        return cuts.map((c, k) => {
+            const status = raw.status[k], actors = batch.docActors[c.doc]
+            const out = { status, clock: {}, spans: null }
+            if (diff) out.patches = null
+            if (status !== 0) return out
+            for (let a = 0; a < actors.length; a++) if (raw.clocksOut[k * na + a]) out.clock[actors[a]] = raw.clocksOut[k * na + a]
+            if (Number(cut.logOff[k + 1]) > Number(cut.logOff[k])) out.spans = decodeSpans(cut, raw.result, k) /* (a version without any op holds no text list yet) */
+            if (diff) out.patches = [].concat(...decodePatches(whole, rawDiff.result, k).slice(rawDiff.nKept[k]))
+            return out
+        })
+    }
+    /**
      * A replica handle with the reference's per-replica calls; all handles of one engine are merged in ONE launch.
      * docId groups the replicas of a document (shared actor / comment ranks); actorId is needed for change().
      */
@@ -1254,4 +1305,4 @@ class MergeEngine {
     }
 }
 
-module.exports = { MergeEngine, encodeDocs, encodeInputOps, packEnvelope, unpackEnvelope, decodeSpans, decodePatches, decodeChanges, decodeRoot, MAPV, prosemirrorDocFromSpans, PATCH, census, ACT, IN, MARK_NAMES, SIDE_NAMES, ATTR, STATUS_MESSAGES, ROOT, HEAD }
+module.exports = { MergeEngine, encodeDocs, encodeInputOps, packEnvelope, unpackEnvelope, decodeSpans, decodePatches, decodeChanges, decodeRoot, MAPV, prosemirrorDocFromSpans, PATCH, census, ACT, IN, MARK_NAMES, SIDE_NAMES, ATTR, STATUS_MESSAGES, ROOT, HEAD, VERSION_ALL }
