@@ -285,7 +285,10 @@ typedef struct ptx_dresult ptx_dresult;  /* result buffers resident in HBM */
                                     the marks of the batch alone.  By default a resident batch remembers, per log, the prefix of changes whose seq / deps checks
                                     passed in an earlier launch of any context (its columns never change, so they pass again) and a launch walks only the changes
                                     behind it: none for a batch merged before, the appended ones for a batch grown by ptx_batch_append[_device].  Results are the
-                                    same either way; a log that fails is walked and reported again in every launch.  For measurement and tests */
+                                    same either way; a log that fails is walked and reported again in every launch.  The same holds for the ROW INDEX of the
+                                    batch (ptx_merge below): a launch of such a context neither writes nor reads it and classifies every row — "a launch as
+                                    the library did before it remembered anything", i.e. what a batch's first merge costs, at will.  The diagnostic launches
+                                    (ptx_merge_phase_cycles) stay out of both as well.  For measurement and tests */
 
 /* ---- lifecycle ---- */
 uint32_t ptx_abi_version(void);
@@ -337,9 +340,18 @@ void ptx_dresult_free(ptx_ctx* ctx, ptx_dresult* r);
  * after them} — written by the first launch in which all of the log's changes pass applyChange's seq / deps checks (micromerge.ts:499-511: the reference, too,
  * checks a change once, when it arrives, against a clock that is replica state).  A later launch of ANY context on that batch reads the mark instead of the
  * envelope; ptx_batch_append[_device] hands the marks of `base` to the grown batch (documents of up to three actors), whose next launch checks the appended
- * changes only.  This is the ONE thing a merge writes into a batch; a batch's columns stay immutable.  A log that fails writes no mark: it is walked, and fails
- * with the same status and row, in every launch.  Results never depend on the marks (PTX_FLAG_READMIT: ignore them); launches on several streams may share a
- * batch — a mark is one aligned 16-byte store, and every value a launch can read there is true. */
+ * changes only.  A log that fails writes no mark: it is walked, and fails with the same status and row, in every launch.  Results never depend on the marks
+ * (PTX_FLAG_READMIT: ignore them); launches on several streams may share a batch — a mark is one aligned 16-byte store, and every value a launch can read
+ * there is true.
+ * The rows are classified once, too: a batch that owns its columns and whose logs all have 16-bit id keys carries a ROW INDEX on the device (about 4.1 bytes per
+ * row) — per log the lists the row pass derives from op_id / action / mark_type and the header: the inserts, the deletes, the mark ops by type as
+ * `row | id key << 16`, and the add / remove bitmap.  The FIRST eligible ptx_merge of the batch writes it, for every log that passes the row pass's checks
+ * (census against the header, malformed rows, repeated op ids), and records an event behind its launches; a later ptx_merge reads it instead of the rows if it
+ * is ordered after that whole launch — on the writer's stream by stream order, on another stream once the event has completed (until then such a merge simply
+ * classifies its rows as before: nothing waits).  A log that fails a check is never indexed and fails with the same status and row in every launch.  A batch
+ * made by ptx_batch_append[_device] starts with an empty index of its own.  No index: ptx_batch_wrap_device, ptx_apply_materialize (merged once), batches
+ * with a wide-key log, the logs beyond one CU's LDS, and a batch whose index could not be allocated (no error).
+ * The marks and the index are the TWO things a merge writes into a batch; a batch's columns stay immutable, and results never depend on either. */
 ptx_status ptx_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r);
 /* Same, `iters` times back to back, bracketed by HIP events on the context's stream:
  * *ms_total = elapsed milliseconds of the `iters` launches (for roofline accounting). */

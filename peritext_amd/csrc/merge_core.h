@@ -159,7 +159,53 @@ struct PtxMergeArgs {
                               (round 6: the replay and change() on such logs) */
     ptx_adm_mark* adm_marks; /* optional [n_logs]: the admission marks of the batch (see ptx_adm_mark); nullptr = every change is walked, nothing is recorded (batches that
                                 do not own their columns, PTX_FLAG_READMIT, the diagnostic launches).  biglog_core.h ignores it */
+    /* the row index of the batch (see ptx_row_index_off below): all three nullptr / 0 = no index, every launch classifies every row and parks in the result's
+     * span rows.  The HOST decides per launch whether the kernel writes the index (row_index_write != 0: exactly one launch per batch ever does) or may read it */
+    uint32_t* row_index;      /* optional: the list words of every log */
+    uint32_t* row_index_bits; /* with it: the add / remove bitmaps of the logs' mark ops */
+    uint32_t* rows_indexed;   /* with it [n_logs]: N once the log's index stands, else 0 */
+    uint32_t row_index_write;
 };
+
+/* ---- the row index of one log of a resident batch: what the row pass P1 has derived from op_id / action / mark_type and the log's header, columns that no entry
+ *      point may modify.  Per log with 16-bit id keys a region of list words `row | id key << 16` in a device block beside the batch (the library's own; never
+ *      zeroed: rows_indexed says which regions hold anything):
+ *        [0, n)                 the inserts, in the order the writing launch listed them (the region starts 16-byte aligned: written and read four words at a time;
+ *                               the words up to n4 = (n + 3) & ~3 belong to this part: a last group of four may hold junk behind the n-th word)
+ *        [n4, n4 + D)           the deletes                                   (the "park" of P3a)
+ *        [n4 + D, n4 + D + K)   the mark ops, grouped by type as in the park  (the "park" of P5a / P5b / P5c)
+ *      n + D + K <= N, so n4 + D + K <= N + 3, and the region of log l holds N + 5 words at least: it starts at word ptx_row_index_off(row offset, l).  The bitmap "mark op k is an addMark"
+ *      — (K >> 5) + 1 words — lives in a second block at word ptx_row_bits_off(row offset, l).  rows_indexed[l] == N (the log's row count) says that a launch has
+ *      written both AFTER the census, the malformed-row check and the duplicate-id check passed: a launch that reads it repeats none of them.  ---- */
+PTX_HD uint64_t ptx_row_index_off(uint64_t row_off, uint64_t log) { return (row_off + 8u * log + 3u) & ~3ull; }
+PTX_HD uint64_t ptx_row_index_words(uint64_t n_ops, uint64_t n_logs) { return ptx_row_index_off(n_ops, n_logs) + 8u; }
+PTX_HD uint64_t ptx_row_bits_off(uint64_t row_off, uint64_t log) { return (row_off >> 5) + log; }
+PTX_HD uint64_t ptx_row_bits_words(uint64_t n_ops, uint64_t n_logs) { return (n_ops >> 5) + n_logs + 1u; }
+/* a log takes the full row pass (not the indexed one): counted by the CPU test-suite's driver of the index, nothing anywhere else */
+#ifndef PTX_NOTE_FULL_ROW_PASS
+#define PTX_NOTE_FULL_ROW_PASS() ((void)0)
+#endif
+/* four consecutive list words of the index, group g_ (words 4 g_ ..): the machine's header has the 16-byte load */
+#ifndef PTX_IDX_LOAD4
+/* (all four words whatever n_ is, as the machine's 16-byte load: the words behind the n_-th are inside the inserts' part of the region; the caller masks them) */
+#define PTX_IDX_LOAD4(a_, b_, c_, d_, p_, g_, n_)                         \
+    a_ = (p_)[4u * (g_)];                                                 \
+    b_ = (p_)[4u * (g_) + 1u];                                            \
+    c_ = (p_)[4u * (g_) + 2u];                                            \
+    d_ = (p_)[4u * (g_) + 3u];
+#endif
+/* the writing launch: group g_ of the insert words from the two LDS lists (rows il_, keys kl_; entries behind the n_-th are 0) and out, four words at once */
+#ifndef PTX_IDX_PACK4
+#define PTX_IDX_PACK4(w_, il_, kl_, g_, n_)                                                                      \
+    for (uint32_t q_ = 0; q_ < 4u; ++q_) {                                                                       \
+        const uint32_t j_ = 4u * (g_) + q_;                                                                      \
+        w_[q_] = j_ < (n_) ? (uint32_t)(il_)[j_] | ((uint32_t)(kl_)[j_] << 16) : 0u;                             \
+    }
+#endif
+#ifndef PTX_IDX_STORE4
+#define PTX_IDX_STORE4(p_, g_, w_) \
+    for (uint32_t q_ = 0; q_ < 4u; ++q_) (p_)[4u * (g_) + q_] = w_[q_];
+#endif
 
 #define PTX_END 0xFFFFu
 #ifndef PTX_S
@@ -980,7 +1026,10 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
     ptx_log_hdr hd_early = ptx_log_hdr();
     constexpr bool kMarks = !kDiag; /* (the diagnostic builds neither read nor write admission marks: their "P0 admission" stamps keep measuring the walk) */
     ptx_adm_mark mk = {0u, 0u, 0u, 0u};
+    constexpr bool kIdx = !kDiag; /* (nor the row index: their "P1" stamps keep measuring the row pass) */
+    uint32_t rows_ix = 0u;        /* rows_indexed[log]: one scalar load beside the header's */
     if (kShort) {
+        if (kIdx && A.rows_indexed && !A.row_index_write) rows_ix = PTX_CONST_LOAD(&A.rows_indexed[log]);
         if (A.chg_off) {
             chg0_early = A.chg_off[log];
             chg1_early = A.chg_off[log + 1];
@@ -1475,6 +1524,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
     else {
         PTX_REMAT_ROWS();
         hd = ptx_load_log_hdr(&PTX_FRESH_ARGS(A).log_hdr[log]);
+        if (kIdx && PTX_FRESH_ARGS(A).rows_indexed && !PTX_FRESH_ARGS(A).row_index_write) rows_ix = PTX_CONST_LOAD(&PTX_FRESH_ARGS(A).rows_indexed[log]);
     }
     uint32_t n, D, moff1, moff2, moff3, Kc, Kid, K; /* list elements (inserts); deletes; mark ops, listed grouped by type: type t owns [moff_t, moff_{t+1}) */
     PtxElemIndex ix;
@@ -1553,6 +1603,22 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
     }
     uint32_t* const out_rank = kLean ? nullptr : A.out_rank;
     uint32_t* const out_refs = kLean ? nullptr : A.out_refs;
+    /* The row index of a resident batch (ptx_row_index_off): this launch WRITES the log's index (the host has made it the batch's one writer), READS it
+     * (rows_indexed == N: a launch that ended before this one began has listed the rows and checked them) or has nothing to do with it.  Writing or reading,
+     * the park of the deletes and of the mark ops is the log's index region, not its span rows: deletes from word n4 = (n + 3) & ~3, mark type t from n4 + D + moff_t. */
+    const bool idx_read = kIdx && small_keys && PTX_FRESH_ARGS(A).row_index && !PTX_FRESH_ARGS(A).row_index_write && rows_ix == N;
+    const bool idx_on = kIdx && small_keys && PTX_FRESH_ARGS(A).row_index && (PTX_FRESH_ARGS(A).row_index_write || idx_read);
+    /* (the phases that derive their scalars again ask the batch again too: nothing of the index stays in a scalar register across the phases) */
+#define PTX_IDX_PARK(F_) PTX_IDX_PARK_IF(F_, kIdx && small_keys && F_.rows_indexed && (F_.row_index_write || PTX_CONST_LOAD(&F_.rows_indexed[log]) == N))
+#define PTX_IDX_PARK_IF(F_, on_)                                                             \
+    do {                                                                                     \
+        if (on_) {                                                                           \
+            park = F_.row_index + ptx_row_index_off(base, log) + ((n + 3u) & ~3u);           \
+            park_top = N - n; /* (the region has N + 5 words, the park starts at most n + 3 words into it) */ \
+            mp0 = D;                                                                         \
+        }                                                                                    \
+    } while (0)
+    PTX_IDX_PARK_IF(PTX_FRESH_ARGS(A), kIdx && idx_on);
     uint16_t* klist = L;
     uint16_t* bigp = ptx_alloc<uint16_t>(bp, n / (PTX_SMALL_BUCKET + 1u) + 2); /* parents with more than PTX_SMALL_BUCKET children */
     /* parents with two or more children (at most half of the elements' parents); once they are sorted the same words hold the bitmap that ranks a huge bucket */
@@ -1592,6 +1658,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         park = (uint32_t*)out_spans;                                                         \
         park_top = 2u * N - 1u;                                                              \
         mp0 = 2u * N - K;                                                                    \
+        PTX_IDX_PARK(F_);                                                                    \
         d_fused = D < n + 1u ? D : n + 1u;                                                   \
         uint32_t o_ = elem_lds;                                                              \
         ix.ib = PTX_LDS_AT(PtxBitWord, o_);                                                  \
@@ -1654,8 +1721,66 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         ra_[u] = ref_a[i_[u]];                                              \
         dra_[u] = ref_a[di_[u]];                                            \
     }
+    /* ---- P1 of a log whose row index stands: the lists come back from the index.  No row is classified, no census taken, no duplicate looked for (the launch
+     *      that wrote the index did all three, over the same columns), nothing is parked and no global store waited for: the park is complete since before this
+     *      kernel began, so P3a's first deletes go out at once.  What is left: the id bitmap and the two insert lists in LDS, the add / remove bitmap copied in.
+     *      Every row and key that comes out of the index is clamped as if it came from the rows. ---- */
+    if (kIdx && idx_read) {
+        const uint32_t* const ins = park - ((n + 3u) & ~3u); /* the inserts' words: 16-byte aligned */
+        PTX_P3A_DQ(0u, p3_dq)
+        PTX_FOR(w, nw + 1) {
+            PtxBitWord z;
+            z.bits = 0;
+            z.pre = 0;
+            ix.ib[w] = z;
+        }
+        PTX_FOR(w, nwe + 1) delbits[w] = 0;
+        {
+            const uint32_t* const mb = PTX_FRESH_ARGS(A).row_index_bits + ptx_row_bits_off(base, log);
+            PTX_FOR(w, (K >> 5) + 1) maddbits[w] = mb[w];
+        }
+        if (out_rank) { /* (as in the full pass below) */
+            PTX_FOR(i, N) out_rank[base + i] = 0xFFFFFFFFu;
+            PTX_SYNC_FULL();
+        }
+        PTX_LEADER {
+            H->n_ins = n;
+            H->n_applied = n + D + K;
+        }
+        PTX_SYNC_LDS();
+        /* four words per load, two loads per thread and step: both in flight together (up to 1 536 inserts of a three-wave log in one step) */
+        auto put = [&](bool in, uint32_t j, uint32_t w) {
+            if (in && j < n) {
+                const uint32_t r_ = w & 0xFFFFu;
+                const uint32_t key = ptx_min(w >> 16, keyspace - 1u);
+                ilist[j] = (uint16_t)(r_ < N ? r_ : N - 1u);
+                klist[j] = (uint16_t)key;
+                ptx_atomic_or(&ix.ib[key >> 5].bits, 1u << (key & 31u));
+            }
+        };
+        PTX_FORV(g0, (n + 3u) >> 2, 2) {
+            uint32_t a0, a1, a2, a3, b0, b1, b2, b3;
+            const bool in_a = PTX_IN(g0, 0), in_b = PTX_IN(g0, 1);
+            const uint32_t ga = in_a ? PTX_IX(g0, 0) : 0u, gb = in_b ? PTX_IX(g0, 1) : 0u;
+            PTX_IDX_LOAD4(a0, a1, a2, a3, ins, ga, n)
+            PTX_IDX_LOAD4(b0, b1, b2, b3, ins, gb, n)
+            put(in_a, 4u * ga, a0);
+            put(in_a, 4u * ga + 1u, a1);
+            put(in_a, 4u * ga + 2u, a2);
+            put(in_a, 4u * ga + 3u, a3);
+            put(in_b, 4u * gb, b0);
+            put(in_b, 4u * gb + 1u, b1);
+            put(in_b, 4u * gb + 2u, b2);
+            put(in_b, 4u * gb + 3u, b3);
+        }
+        PTX_SYNC_LDS();
+        PTX_P3A_LOAD(0u, p3_i, p3_id, p3_ra, p3_di, p3_dra, p3_dq)
+        PTX_P3A_DQ(1u, p3_dq)
+        ptx_bitwords_prefix<kThreads>(ix.ib, nw + 1, &H->scan_tmp[16]);
+    } else
     /* ---- P1: ONE pass over the rows: id bitmaps, row lists per class ---- */
     {
+        PTX_NOTE_FULL_ROW_PASS();
         uint32_t err4 = 0, ctr_hi = 0, act_hi = 0; /* malformed class bytes; max counter - 1 and max actor met */
         if (!p1_loaded) { PTX_P1_LOAD(PTX_G_OF(0u, p1_steps), id, a4, mt4) } /* (no admission phase ahead: the first rows go out here, while the bitmaps are cleared) */
         /* during this pass ib[w] = {ids of the inserts, ids of ALL ops (duplicate detection)}: one 8-byte LDS atomic per row */
@@ -1814,6 +1939,22 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             ptx_atomic_add(&H->cur[6], distinct);
         }
         PTX_SYNC_LDS();
+        if (kIdx && idx_on && H->err == PTX_NO_ERR && H->cur[6] == N) {
+            /* the launch that writes the log's index: census, malformed-row check and duplicate check have passed (the same answer in every thread: all three
+             * stand behind the barrier above) and the lists are complete in memory (the full barrier above).  The add / remove bitmap goes out and ONE lane
+             * says so; who reads this does so in a LATER kernel (the host's rule, launch_merge), so nothing here needs more than the end of this kernel. */
+            uint32_t* const mb = PTX_FRESH_ARGS(A).row_index_bits + ptx_row_bits_off(base, log);
+            PTX_FOR(w, (K >> 5) + 1) mb[w] = maddbits[w];
+            /* the inserts' words, from the two LDS lists (complete, and untouched until P3a): coalesced 16-byte stores that nothing in this kernel waits for —
+             * one more scattered 4-byte store per insert in front of the row pass's full barrier was 2-3 % of a first merge */
+            uint32_t* const ins = park - ((n + 3u) & ~3u);
+            PTX_FOR(g, (n + 3u) >> 2) {
+                uint32_t w4[4];
+                PTX_IDX_PACK4(w4, ilist, klist, g, n)
+                PTX_IDX_STORE4(ins, g, w4)
+            }
+            PTX_LEADER { PTX_FRESH_ARGS(A).rows_indexed[log] = N; }
+        }
         if (H->err == PTX_NO_ERR && H->cur[6] != N) {
             /* some opId occurs twice (every row had a well-formed id, so N distinct ids were expected): find the
              * first repeated row with a second, returning pass over a cleared bitmap — the rare path */

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <map>
+#include <atomic>
 #include <mutex>
 #include <set>
 #include <unordered_map>
@@ -563,7 +564,9 @@ __global__ void ptx_tile_offsets_kernel(const uint64_t* src, uint64_t* dst, uint
 #define PTX_ENV_PAD 8u
 #define PTX_LDS_GRANULE 1280u /* bytes: the CU's 160 KB in 128 granules */
 
+static std::atomic<uint64_t> g_ctx_serial{0};
 struct ptx_ctx {
+    const uint64_t serial = ++g_ctx_serial; /* never reused, unlike the address of a context or the handle of its stream (launch_merge: who wrote a batch's row index) */
     int device = 0;
     hipStream_t stream = nullptr;     /* the stream in use: own_stream, or the caller's (ptx_set_stream) */
     hipStream_t own_stream = nullptr;
@@ -698,6 +701,15 @@ struct ptx_dbatch {
      * its columns and carries the envelope has them (the columns of such a batch never change: what was admitted stays admitted); the one piece of a batch that
      * a merge WRITES — zeroed when the batch is made, freed with it */
     ptx_adm_mark* adm_marks = nullptr;
+    /* the row index (merge_core.h ptx_row_index_off): what the merge kernel's row pass P1 derives from op_id / action / mark_type and the headers, kept so that
+     * only the FIRST merge of the batch classifies and checks the rows.  Only a batch that owns its columns and whose every LDS-kernel log has 16-bit id keys
+     * has one; the big block is never zeroed (rows_indexed, one word per log, says which logs' regions hold anything).  Beside the marks the second thing a
+     * merge writes into a batch.  Who writes and who may read is decided per launch (launch_merge) from the state below, under g_index_mu. */
+    uint32_t *row_index = nullptr, *row_index_bits = nullptr, *rows_indexed = nullptr;
+    mutable int index_state = 0;               /* 0 nobody has written it; 1 a launch is being enqueued that writes it; 2 written by a launch of context index_writer on index_stream, index_ev recorded behind it; 3 that launch has ended */
+    mutable uint64_t index_writer = 0;         /* ptx_ctx::serial of the writing context */
+    mutable hipStream_t index_stream = nullptr;
+    mutable hipEvent_t index_ev = nullptr;
     /* launch shape derived from the largest log */
     uint32_t max_log_ops = 0;
     uint32_t lds_bytes = 0;
@@ -731,6 +743,17 @@ struct ptx_dresult {
     uint32_t* refs = nullptr; /* with rank: resolved references of the delete / mark rows (PtxMergeArgs.out_refs), for ptx_replay_patches */
     uint32_t* refs_hi = nullptr; /* with refs, for a batch that holds a log of more than 32 766 list elements: the high halves of its mark rows' boundary slots */
 };
+
+static std::mutex g_index_mu;                        /* the index_state / index_stream / index_ev of every batch */
+static void free_row_index(ptx_dbatch* b) {
+    (void)ptx_dev_free(b->row_index);
+    (void)ptx_dev_free(b->row_index_bits);
+    (void)ptx_dev_free(b->rows_indexed);
+    b->row_index = b->row_index_bits = b->rows_indexed = nullptr;
+    if (b->index_ev) (void)hipEventDestroy(b->index_ev);
+    b->index_ev = nullptr;
+    b->index_state = 0;
+}
 
 static thread_local std::string g_create_err;
 
@@ -768,7 +791,7 @@ static void shape_launch(ptx_ctx* ctx, ptx_dbatch* b, uint64_t need, uint32_t ma
 
 /* Census of a resident batch: headers (computed on the device unless the caller supplied them) and the
  * launch shape.  `have_hdr`: b->log_hdr already holds the caller's headers. */
-static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr) {
+static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr, bool want_index = true /* false: a batch that is merged once (ptx_apply_materialize) */) {
     if (b->owns && b->chg_off && b->n_logs && !b->adm_marks) { /* every batch the library makes comes through here once: nothing of it is admitted yet (an append has copied its base's marks before) */
         hipError_t e = ptx_dev_malloc((void**)&b->adm_marks, (size_t)b->n_logs * sizeof(ptx_adm_mark));
         if (e == hipSuccess) e = hipMemsetAsync(b->adm_marks, 0, (size_t)b->n_logs * sizeof(ptx_adm_mark), ctx->stream);
@@ -881,6 +904,21 @@ static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr) {
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return fail(ctx, PTX_ERR_HIP, std::string("launch groups: ") + hipGetErrorString(e));
+    }
+    /* the row index of a batch that owns its columns: ~4.1 bytes per row beside the 32 of the op log; an allocation that fails leaves the batch without one
+     * (every merge then classifies its rows, as before), never with an error.  Only the word per log is zeroed. */
+    if (want_index && b->owns && b->n_logs && b->small_keys && !b->rows_indexed) {
+        hipError_t e = ptx_dev_malloc((void**)&b->rows_indexed, (size_t)b->n_logs * 4);
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&b->row_index, (size_t)ptx_row_index_words(b->n_ops, b->n_logs) * 4);
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&b->row_index_bits, (size_t)ptx_row_bits_words(b->n_ops, b->n_logs) * 4);
+        if (e == hipSuccess) e = hipMemsetAsync(b->rows_indexed, 0, (size_t)b->n_logs * 4, ctx->stream);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->index_ev, hipEventDisableTiming); /* recorded behind the one merge that writes the index (launch_merge) */
+        /* the zeroes stand before the batch is handed out: its first merge may come from another context, on a stream nothing orders behind this one */
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            free_row_index(b);
+        }
     }
     return PTX_OK;
 }
@@ -1080,6 +1118,7 @@ void ptx_batch_free(ptx_ctx* ctx, ptx_dbatch* b) {
     (void)ptx_dev_free(b->chg_env);
     (void)ptx_dev_free(b->chg_env_hi);
     (void)ptx_dev_free(b->adm_marks);
+    free_row_index(b);
     delete b;
 }
 
@@ -1092,7 +1131,7 @@ uint64_t ptx_batch_n_ops(const ptx_dbatch* b) { return b ? b->n_ops : 0; }
 uint64_t ptx_batch_n_changes(const ptx_dbatch* b) { return b && b->chg_off ? b->n_changes : 0; }
 uint32_t ptx_batch_max_actors(const ptx_dbatch* b) { return b && b->chg_off ? b->max_actors : 0; }
 
-ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t copies, ptx_dbatch** out) {
+static ptx_status upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t copies, ptx_dbatch** out, bool want_index) {
     if (!ctx || !out) return PTX_ERR_INVALID_ARG;
     *out = nullptr;
     ptx_status st = check_batch(ctx, h);
@@ -1198,7 +1237,7 @@ ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t cop
         PTX_TRY(e2);
     }
 #undef PTX_TRY
-    st = census_and_shape(ctx, b, h->log_hdr != nullptr);
+    st = census_and_shape(ctx, b, h->log_hdr != nullptr, want_index);
     if (st) {
         ptx_batch_free(ctx, b);
         return st;
@@ -1207,7 +1246,8 @@ ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t cop
     return PTX_OK;
 }
 
-ptx_status ptx_batch_upload(ptx_ctx* ctx, const ptx_batch* host, ptx_dbatch** out) { return ptx_batch_upload_tiled(ctx, host, 1, out); }
+ptx_status ptx_batch_upload_tiled(ptx_ctx* ctx, const ptx_batch* h, uint32_t copies, ptx_dbatch** out) { return upload_tiled(ctx, h, copies, out, true); }
+ptx_status ptx_batch_upload(ptx_ctx* ctx, const ptx_batch* host, ptx_dbatch** out) { return upload_tiled(ctx, host, 1, out, true); }
 
 ptx_status ptx_batch_append_device(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dbatch* m, ptx_dbatch** out) {
     if (!ctx || !base || !m || !out) return PTX_ERR_INVALID_ARG;
@@ -1413,6 +1453,35 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
     A.grid_bar = nullptr;
     /* (the diagnostic launches measure the walk; PTX_FLAG_READMIT asks for it) */
     A.adm_marks = admit && !(ctx->flags & PTX_FLAG_READMIT) && !ctx->clocks && !ctx->stop_after ? b->adm_marks : nullptr;
+    /* The row index.  The order of a log's lists differs from launch to launch (their slots come from one LDS atomic per wave), so two launches writing one
+     * log's region at once would interleave two permutations: exactly ONE launch per batch ever writes — the first eligible ptx_merge (its main / rest launches
+     * write disjoint logs and count as one writer).  A launch READS the index only if it is ordered after the WHOLE kernel that wrote it: a later launch on the
+     * writer's stream by stream order, a launch on another stream once hipEventQuery says the event recorded behind the writer has completed.  So what a reader
+     * sees was complete before its kernel began, and no argument about visibility between XCDs inside a kernel is needed.  Until then a launch on another
+     * stream neither reads nor writes: it parks in its result's span rows, as before — nothing waits.  PTX_FLAG_READMIT and the diagnostic launches stay out
+     * altogether, like with the marks. */
+    int idx_mode = 0; /* 1 write, 2 read */
+    if (b->row_index && !(ctx->flags & PTX_FLAG_READMIT) && !ctx->clocks && !ctx->stop_after) {
+        std::lock_guard<std::mutex> g(g_index_mu);
+        if (b->index_state == 0) { /* (the event was made with the index: a driver call here would stand between the caller and its first merge) */
+            b->index_state = 1;
+            b->index_writer = ctx->serial;
+            b->index_stream = ctx->stream;
+            idx_mode = 1;
+        } else if (b->index_state == 2) {
+            /* the writing context itself, still on the stream it wrote on (ptx_set_stream drains the stream it leaves): stream order, and no driver call in
+             * its launch path.  A context's serial is never reused, so a stream handle that comes back after a context was destroyed cannot pass for it */
+            if (b->index_writer == ctx->serial && b->index_stream == ctx->stream) idx_mode = 2;
+            else if (hipEventQuery(b->index_ev) == hipSuccess) {
+                b->index_state = 3;
+                idx_mode = 2;
+            } else (void)hipGetLastError(); /* (hipErrorNotReady) */
+        } else if (b->index_state == 3) idx_mode = 2;
+    }
+    A.row_index = idx_mode ? b->row_index : nullptr;
+    A.row_index_bits = idx_mode ? b->row_index_bits : nullptr;
+    A.rows_indexed = idx_mode ? b->rows_indexed : nullptr;
+    A.row_index_write = idx_mode == 1 ? 1u : 0u;
     /* one workgroup per log; far more workgroups than the 256 CUs so the dispatcher load-balances.  Up to three launches (census_and_shape): the many at
      * their LDS window, the few that need a larger one, the logs beyond one CU's LDS through the HBM-staged kernel — the latter two on a side stream forked
      * from and joined to the caller's, so that they run beside the many instead of after them. */
@@ -1485,6 +1554,11 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
         (void)hipEventRecord(ctx->ev_join, ctx->side);
         (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
     }
+    if (idx_mode == 1) { /* behind every launch of this merge (the side stream has been joined): from here on others may learn that the index stands */
+        std::lock_guard<std::mutex> g(g_index_mu);
+        if (hipEventRecord(b->index_ev, ctx->stream) == hipSuccess) b->index_state = 2;
+        else (void)hipGetLastError(); /* (state 1 for good: nobody reads, nobody writes again) */
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, PTX_ERR_HIP, std::string("ptx_merge_kernel launch: ") + hipGetErrorString(e));
     return PTX_OK;
@@ -1495,6 +1569,21 @@ ptx_status ptx_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r) {
     if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
     PTX_HIP(ctx, ptx_enter(ctx));
     return launch_merge(ctx, b, r);
+}
+
+/* Test hook, NOT part of the C ABI (no declaration in the header; the GPU suite binds it by name): where the row index of a batch stands.  Returns -1 for a
+ * batch without an index, else the host's state (0 nobody has written it .. 3 the writing merge has ended); *n_indexed = the logs whose rows_indexed is set,
+ * read after everything this context has enqueued. */
+int ptx_debug_row_index(ptx_ctx* ctx, const ptx_dbatch* b, uint32_t* n_indexed) {
+    if (n_indexed) *n_indexed = 0;
+    if (!ctx || !b || !b->rows_indexed) return -1;
+    if (ptx_enter(ctx) != hipSuccess) return -1;
+    std::vector<uint32_t> h(b->n_logs);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(h.data(), b->rows_indexed, (size_t)b->n_logs * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (n_indexed)
+        for (uint32_t v : h) *n_indexed += v != 0u;
+    std::lock_guard<std::mutex> g(g_index_mu);
+    return b->index_state;
 }
 
 ptx_status ptx_merge_timed(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r, uint32_t iters, float* ms_total) {
@@ -1960,7 +2049,7 @@ ptx_status ptx_apply_materialize(ptx_ctx* ctx, const ptx_batch* batch, ptx_resul
     memset(out, 0, sizeof(*out));
     ptx_dbatch* b = nullptr;
     ptx_dresult* r = nullptr;
-    ptx_status st = ptx_batch_upload(ctx, batch, &b);
+    ptx_status st = upload_tiled(ctx, batch, 1, &b, false); /* merged once: an index would be written and never read */
     if (st == PTX_OK) st = ptx_result_alloc(ctx, b, &r);
     if (st == PTX_OK) st = ptx_merge(ctx, b, r);
     if (st == PTX_OK) st = ptx_result_download(ctx, b, r, out);

@@ -566,6 +566,36 @@ typedef uint32_t ptx_u32_a1 __attribute__((aligned(1)));
         }                                                                              \
     }
 #define PTX_P1_BYTES(col_, r0_, dst_, n_) dst_ = PTX_STREAM_LOAD((const ptx_u32_a1*)(col_ + ((r0_) < (n_) ? (r0_) : (n_) - 1u)));
+/* four consecutive list words of a log's row index (merge_core.h ptx_row_index_off: the insert words start 16-byte aligned and the region has room behind them):
+ * ONE 16-byte load; the words past the n_-th are whatever the region holds, the caller masks them */
+#define PTX_IDX_LOAD4(a_, b_, c_, d_, p_, g_, n_)                                      \
+    {                                                                                  \
+        const ptx_u32x4 q_ = *(const ptx_u32x4*)((p_) + 4u * (g_));                    \
+        a_ = q_.x;                                                                     \
+        b_ = q_.y;                                                                     \
+        c_ = q_.z;                                                                     \
+        d_ = q_.w;                                                                     \
+    }
+/* the writing launch's side of it: group g_ of the insert words packed from the LDS lists of rows and keys (both 16-byte aligned: two 8-byte LDS reads; the last
+ * group reads up to three entries past the n_-th, inside the log's window, and zeroes them) and stored with ONE 16-byte store */
+#define PTX_IDX_PACK4(w_, il_, kl_, g_, n_)                                            \
+    {                                                                                  \
+        const uint64_t r_ = *(const uint64_t*)((il_) + 4u * (g_));                     \
+        const uint64_t k_ = *(const uint64_t*)((kl_) + 4u * (g_));                     \
+        _Pragma("unroll") for (uint32_t q_ = 0; q_ < 4u; ++q_) {                       \
+            const uint32_t v_ = ((uint32_t)(r_ >> (16u * q_)) & 0xFFFFu) | (((uint32_t)(k_ >> (16u * q_)) & 0xFFFFu) << 16); \
+            w_[q_] = 4u * (g_) + q_ < (n_) ? v_ : 0u;                                  \
+        }                                                                              \
+    }
+#define PTX_IDX_STORE4(p_, g_, w_)                                                     \
+    {                                                                                  \
+        ptx_u32x4 q_;                                                                  \
+        q_.x = w_[0];                                                                  \
+        q_.y = w_[1];                                                                  \
+        q_.z = w_[2];                                                                  \
+        q_.w = w_[3];                                                                  \
+        *(ptx_u32x4*)((p_) + 4u * (g_)) = q_;                                          \
+    }
 
 /* ---- gen_core.h / change_core.h: ONE wave per workgroup ---- */
 /* 64-wide ballot over lanes: `expr` may use `lane_` */
