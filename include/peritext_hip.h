@@ -635,6 +635,43 @@ ptx_status ptx_sync_replicas(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_pa
 ptx_status ptx_batch_at_versions(ptx_ctx* ctx, const ptx_dbatch* base, uint32_t n_cuts, const uint32_t* src_log, const uint32_t* clocks, const uint32_t* prefix,
                                  uint32_t flags, ptx_dbatch** out, uint32_t* status_out, uint32_t* n_kept_out, uint32_t* first_row_out, uint32_t* clocks_out);
 
+/* ---- document text: what getTextWithFormatting returns is {text, marks}[] (peritext.ts:337-395; addCharactersToSpans :438-455) ----
+ * ptx_result carries value IDS, and a span's `start` is an ELEMENT index: a value is any JS string (one character, a pasted paragraph inserted as one value —
+ * test/micromerge.ts:202 —, the empty string, half of a surrogate pair), so a host had to join the text one table lookup per visible element.  With the string
+ * table resident the device assembles ONE UTF-16 buffer per downloaded range, and a host builds each FormatSpanWithText.text with a single slice:
+ *   text of log l     text[text_off[l] .. text_off[l + 1]) = the concatenation of string[values[i]] over the log's n_visible elements in document order
+ *   text of span k    the log's text from span_unit[span_off[l] + k] to span_unit[span_off[l] + k + 1] (the last span: to the log's length text_off[l + 1] -
+ *                     text_off[l]).  An element whose string is empty is still an element: a span made only of such elements has span_unit equal to its successor's.
+ * Units are UTF-16 CODE UNITS (JS string semantics, not code points); lone surrogates are legal and copied as they are.
+ * Per-log status (the other logs of the range are never affected):
+ *   the log's merge status   a log the merge failed has no text and no spans
+ *   PTX_ERR_BAD_OP           a value id >= n_strings.  Every id is checked before anything is read through it: never an out-of-range read.  No text; the spans of
+ *                            the merge stay counted in span_off (it equals ptx_result.span_off of the same range), their span_unit is 0
+ *   PTX_ERR_CAPACITY         the log's text reaches 2^32 code units (span_unit is 32 bits wide).  No text, as above
+ * n_logs == 0 returns an empty result (text_off = span_off = {0}); a range outside the batch is PTX_ERR_INVALID_ARG.  `r` = ptx_merge of `b`, enqueued on this
+ * context's stream or complete; elem_rank is not needed (PTX_FLAG_NO_ELEM_RANK contexts work).  The insert payloads of a batch made by ptx_generate are character
+ * codes: a table of 128 one-unit strings (or 65 536 of them) serves it. */
+typedef struct ptx_dstrings ptx_dstrings;   /* a string table resident in HBM */
+/* units: the UTF-16 code units of all strings back to back; off: [n_strings + 1], off[0] == 0, monotonic (else PTX_ERR_INVALID_ARG).  HOST pointers; copied before
+ * the call returns.  n_strings == 0 is legal (every value id is then PTX_ERR_BAD_OP). */
+ptx_status ptx_strings_upload(ptx_ctx* ctx, const uint16_t* units, const uint64_t* off, uint32_t n_strings, ptx_dstrings** out);
+void ptx_strings_free(ptx_ctx* ctx, ptx_dstrings* s);
+typedef struct ptx_text {
+    uint32_t n_logs;
+    uint32_t reserved;
+    float kernel_ms;               /* HIP-event duration of the length (+ offset scan) and assemble launches */
+    uint32_t reserved2;
+    const uint32_t* status;        /* [n_logs] PTX_OK, the log's merge status, PTX_ERR_BAD_OP, PTX_ERR_CAPACITY */
+    const uint64_t* text_off;      /* [n_logs + 1] code units */
+    const uint16_t* text;          /* [text_off[n_logs]] */
+    const uint64_t* span_off;      /* [n_logs + 1] == ptx_result.span_off of the same range */
+    const uint32_t* span_unit;     /* [span_off[n_logs]] code-unit offset, within the log's text, of the first element of span k */
+    void* owner;
+} ptx_text;
+/* The text of the logs [first_log, first_log + n_logs).  Synchronises.  Owned by the library until ptx_text_free. */
+ptx_status ptx_result_text_range(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, ptx_text* out);
+void ptx_text_free(ptx_text* t);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

@@ -255,6 +255,26 @@ class ptx_host_batch(C.Structure):
     _fields_ = [("b", ptx_batch), ("owner", C.c_void_p)]
 
 
+# document text (ptx_result_text_range; peritext_amd/csrc/text_core.h)
+TEXT_TILE = 256  # PTX_TEXT_TILE: visible elements per step of the assemble walk
+TEXT_LANE_MAX = 16  # PTX_TEXT_LANE_MAX: a value of more code units than this is copied by the whole wave
+
+
+class ptx_text(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("reserved2", C.c_uint32),
+        ("status", u32p),
+        ("text_off", u64p),
+        ("text", u16p),
+        ("span_off", u64p),
+        ("span_unit", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
 # numpy dtypes with the same layout
 import numpy as np  # noqa: E402
 
@@ -342,6 +362,10 @@ FUNCTIONS = {
     "ptx_batch_max_actors": (C.c_uint32, [vp]),
     "ptx_batch_download": (C.c_int32, [vp, vp, C.POINTER(ptx_host_batch)]),
     "ptx_host_batch_free": (None, [C.POINTER(ptx_host_batch)]),
+    "ptx_strings_upload": (C.c_int32, [vp, u16p, u64p, C.c_uint32, C.POINTER(vp)]),
+    "ptx_strings_free": (None, [vp, vp]),
+    "ptx_result_text_range": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(ptx_text)]),
+    "ptx_text_free": (None, [C.POINTER(ptx_text)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

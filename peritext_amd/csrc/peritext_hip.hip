@@ -37,6 +37,7 @@
 #include "sync_core.h"
 #include "version_core.h"
 #include "accum_core.h"
+#include "text_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -545,6 +546,52 @@ extern "C" __global__ void __launch_bounds__(64) ptx_result_compact_kernel(const
     const uint32_t* cs = (const uint32_t*)(cints + b);
     uint32_t* cd = (uint32_t*)(dcints + oc);
     for (uint32_t i = threadIdx.x; i < 3u * r.n_cintervals; i += 64u) cd[i] = cs[i];
+}
+
+/* ---- document text (text_core.h): one wave per log of the range computes the log's length in code units and checks its value ids against the string table;
+ *      one workgroup scans lengths and span counts into text_off / span_off (in place, a chunk of 1 024 logs per step); one wave per log assembles the text ---- */
+extern "C" __global__ void __launch_bounds__(64) ptx_text_length_kernel(PtxTextArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_text_lds[PTX_TEXT_LDS_BYTES];
+    if (blockIdx.x < A.n_logs) ptx_text_length_log<64>(A, blockIdx.x, ptx_text_lds);
+}
+extern "C" __global__ void __launch_bounds__(1024) ptx_text_offsets_kernel(uint64_t* off /* [2][n_logs + 1]: counts in, exclusive prefix sums out */, uint32_t n_logs) {
+    __shared__ uint64_t wsum[2][16];
+    __shared__ uint64_t run[2];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x < 2) run[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t c0 = 0; c0 < n_logs; c0 += 1024u) {
+        const uint32_t l = c0 + threadIdx.x;
+        uint64_t v[2] = {0, 0}, incl[2];
+        for (int k = 0; k < 2; ++k) {
+            if (l < n_logs) v[k] = off[(uint64_t)k * (n_logs + 1) + l];
+            uint64_t x = v[k];
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint64_t y = __shfl_up(x, d, 64);
+                if ((int)lane >= d) x += y;
+            }
+            incl[k] = x;
+            if (lane == 63u) wsum[k][wave] = x;
+        }
+        __syncthreads();
+        for (int k = 0; k < 2; ++k) {
+            uint64_t base = run[k];
+            for (uint32_t w = 0; w < wave; ++w) base += wsum[k][w];
+            if (l < n_logs) off[(uint64_t)k * (n_logs + 1) + l] = base + incl[k] - v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            uint64_t t = 0;
+            for (uint32_t w = 0; w < 16u; ++w) t += wsum[threadIdx.x][w];
+            run[threadIdx.x] += t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) off[(uint64_t)threadIdx.x * (n_logs + 1) + n_logs] = run[threadIdx.x];
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_text_assemble_kernel(PtxTextArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_text_lds[PTX_TEXT_LDS_BYTES];
+    if (blockIdx.x < A.n_logs) ptx_text_assemble_log<64>(A, blockIdx.x, ptx_text_lds);
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -2020,6 +2067,149 @@ ptx_status ptx_result_download_range(ptx_ctx* ctx, const ptx_dbatch* b, const pt
 ptx_status ptx_result_download(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, ptx_result* out) {
     if (!r) return PTX_ERR_INVALID_ARG;
     return ptx_result_download_range(ctx, b, r, 0, r->n_logs, out);
+}
+
+/* ---- document text: the resident string table and the assembled text of a range of logs (text_core.h) ---- */
+struct ptx_dstrings {
+    uint16_t* units = nullptr; /* device: the code units of all strings back to back */
+    uint64_t* off = nullptr;   /* device [n + 1] */
+    uint32_t n = 0;
+    uint64_t n_units = 0;
+};
+
+ptx_status ptx_strings_upload(ptx_ctx* ctx, const uint16_t* units, const uint64_t* off, uint32_t n_strings, ptx_dstrings** out) {
+    if (!ctx || !out) return PTX_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (n_strings && !off) return fail(ctx, PTX_ERR_INVALID_ARG, "string table without offsets");
+    const uint64_t zero = 0;
+    if (!n_strings) off = &zero;
+    if (off[0] != 0) return fail(ctx, PTX_ERR_INVALID_ARG, "string offsets do not start at 0");
+    for (uint32_t i = 0; i < n_strings; ++i)
+        if (off[i + 1] < off[i]) return fail(ctx, PTX_ERR_INVALID_ARG, "string offsets are not monotonic");
+    const uint64_t nu = off[n_strings];
+    if (nu && !units) return fail(ctx, PTX_ERR_INVALID_ARG, "string table without code units");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_dstrings* s = new ptx_dstrings();
+    s->n = n_strings;
+    s->n_units = nu;
+    hipError_t e = ptx_dev_malloc((void**)&s->units, std::max<uint64_t>(nu, 1) * 2);
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&s->off, ((uint64_t)n_strings + 1) * 8);
+    if (e == hipSuccess && nu) e = hipMemcpyAsync(s->units, units, nu * 2, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->off, off, ((uint64_t)n_strings + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* the caller's arrays are pageable and free to go once this returns */
+    else (void)hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)ptx_dev_free(s->units);
+        (void)ptx_dev_free(s->off);
+        delete s;
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("string table upload: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return PTX_OK;
+}
+void ptx_strings_free(ptx_ctx* ctx, ptx_dstrings* s) {
+    if (!s) return;
+    if (ctx) (void)ptx_enter(ctx);
+    (void)ptx_dev_free(s->units);
+    (void)ptx_dev_free(s->off);
+    delete s;
+}
+
+void ptx_text_free(ptx_text* t) {
+    if (!t) return;
+    delete (ptx_host_result*)t->owner;
+    memset(t, 0, sizeof(*t));
+}
+
+ptx_status ptx_result_text_range(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, ptx_text* out) {
+    if (!ctx || !b || !r || !s || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
+    if ((uint64_t)first_log + n_logs > r->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "log range exceeds the result");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_host_result* h = new ptx_host_result();
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0: the statuses and the two offset rows (text_off, span_off) — device and pinned host alike */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), blk0 = st_bytes + a16(2 * no * 8);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, blk0);
+    uint64_t* offs = (uint64_t*)(hp0 + st_bytes);
+    float ms_len = 0.f, ms_asm = 0.f;
+    uint64_t tu = 0, ts = 0;
+    PtxTextArgs A;
+    memset(&A, 0, sizeof(A));
+    if (e == hipSuccess) {
+        A.log_off = b->log_off;
+        A.logs = r->logs;
+        A.values = r->values;
+        A.spans = r->spans;
+        A.units = s->units;
+        A.str_off = s->off;
+        A.n_strings = s->n;
+        A.first_log = first_log;
+        A.n_logs = n_logs;
+        A.status = (uint32_t*)d0;
+        A.off = (uint64_t*)(d0 + st_bytes);
+    }
+    if (e == hipSuccess && n_logs) {
+        e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_length_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0, d0, blk0, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms_len, ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) {
+            tu = offs[n_logs];
+            ts = offs[no + n_logs];
+            if (ts > r->n_rows) e = hipErrorInvalidValue; /* (a log never produces more rows than it has ops) */
+        }
+    } else if (e == hipSuccess) {
+        offs[0] = offs[1] = 0; /* an empty range: text_off = span_off = {0} */
+    }
+    /* block 1: the text and the spans' unit offsets */
+    const uint64_t tx_bytes = a16(tu * 2), blk1 = tx_bytes + a16(ts * 4) + 16;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk1, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    if (e == hipSuccess && n_logs) {
+        e = ptx_dev_malloc((void**)&d1, blk1);
+        if (e == hipSuccess) {
+            A.text = (uint16_t*)d1;
+            A.span_unit = (uint32_t*)(d1 + tx_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_assemble_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess && tu) e = hipMemcpyAsync(hp1, d1, tu * 2, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && ts) e = hipMemcpyAsync(hp1 + tx_bytes, d1 + tx_bytes, ts * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms_asm, ctx->ev0, ctx->ev1);
+    }
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("document text: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->kernel_ms = ms_len + ms_asm;
+    out->status = (const uint32_t*)hp0;
+    out->text_off = offs;
+    out->span_off = offs + no;
+    out->text = (const uint16_t*)hp1;
+    out->span_unit = (const uint32_t*)(hp1 + tx_bytes);
+    out->owner = h;
+    return PTX_OK;
 }
 
 ptx_status ptx_result_download_logs(ptx_ctx* ctx, const ptx_dresult* r, ptx_log_result* out, uint32_t n_logs) {

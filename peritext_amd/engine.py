@@ -315,6 +315,43 @@ class Engine:
         finally:
             self.lib.ptx_result_free(C.byref(res))
 
+    # ---- document text ----
+    def upload_strings(self, values):
+        """A string table made resident (ptx_strings_upload): `values` = the batch's string table (wire.Batch.values), JS strings — UTF-16 code
+        units, lone surrogates allowed.  Returns the handle Engine.text takes; free it with free_strings."""
+        enc = [v.encode("utf-16-le", "surrogatepass") for v in values]
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        if enc:
+            off[1:] = np.cumsum([len(e) // 2 for e in enc], dtype=np.uint64)
+        units = np.frombuffer(b"".join(enc), dtype="<u2") if int(off[-1]) else np.zeros(1, dtype=np.uint16)
+        h = C.c_void_p()
+        self._check(self.lib.ptx_strings_upload(self.ctx, units.ctypes.data_as(abi.u16p), off.ctypes.data_as(abi.u64p), len(enc), C.byref(h)))
+        return h
+
+    def free_strings(self, h):
+        self.lib.ptx_strings_free(self.ctx, h)
+
+    def text(self, dbatch, dresult, dstrings, first_log=0, n_logs=None):
+        """The text of the logs [first_log, first_log + n_logs) assembled on the device (ptx_result_text_range): wire.Text — one UTF-16 buffer, per-log
+        offsets into it and per span the code-unit offset of its first character, so that a span's text is one slice (wire.decode_spans_text)."""
+        if n_logs is None:
+            n_logs = self.n_logs(dbatch) - first_log
+        t = abi.ptx_text()
+        self._check(self.lib.ptx_result_text_range(self.ctx, dbatch, dresult, dstrings, first_log, n_logs, C.byref(t)))
+        try:
+            n = int(t.n_logs)
+
+            def arr(ptr, dtype, count):
+                if count == 0:
+                    return np.zeros(0, dtype=dtype)
+                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+
+            text_off, span_off = arr(t.text_off, np.uint64, n + 1), arr(t.span_off, np.uint64, n + 1)
+            return wire.Text(status=arr(t.status, np.uint32, n), text_off=text_off, text=arr(t.text, np.uint16, int(text_off[n])), span_off=span_off,
+                             span_unit=arr(t.span_unit, np.uint32, int(span_off[n])), kernel_ms=float(t.kernel_ms))
+        finally:
+            self.lib.ptx_text_free(C.byref(t))
+
     def replay_patches(self, dbatch, dresult, first_row=None):
         """The Patch[] stream every applyChange of every log would have returned (reference/src/micromerge.ts:499),
         as wire.Patches; `dresult` = the merge of the same batch (engine created without FLAG_NO_ELEM_RANK).

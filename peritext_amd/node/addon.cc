@@ -84,6 +84,11 @@ struct Lib {
     /* patch streams back into canonical rows; the fuzzer's patch assertion on the device */
     ptx_status (*accumulate_patches)(ptx_ctx*, const ptx_dbatch*, const ptx_patches*, ptx_result*) = nullptr;
     ptx_status (*check_patches)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, ptx_patch_check_log*, uint64_t*) = nullptr;
+    /* document text assembled on the device */
+    ptx_status (*strings_upload)(ptx_ctx*, const uint16_t*, const uint64_t*, uint32_t, ptx_dstrings**) = nullptr;
+    void (*strings_free)(ptx_ctx*, ptx_dstrings*) = nullptr;
+    ptx_status (*result_text_range)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, ptx_text*) = nullptr;
+    void (*text_free)(ptx_text*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -132,7 +137,8 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.result_download_logs, "ptx_result_download_logs") && sym(L.root_map, "ptx_root_map") && sym(L.root_maps_free, "ptx_root_maps_free") && sym(L.device_alloc, "ptx_device_alloc") && sym(L.device_free, "ptx_device_free") &&
                   sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device") &&
                   sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches") &&
-                  sym(L.batch_at_versions, "ptx_batch_at_versions");
+                  sym(L.batch_at_versions, "ptx_batch_at_versions") && sym(L.strings_upload, "ptx_strings_upload") && sym(L.strings_free, "ptx_strings_free") &&
+                  sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -515,6 +521,98 @@ napi_value ResidentFree(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+/* ---- document text assembled on the device (INTEGRATION.md "Text on the device"): stringsUpload(ctx, units: Uint16Array, off: BigUint64Array) -> handle of a
+ *      resident string table (ptx_strings_upload); stringsFree(ctx, handle); resultText(ctx, batch, strings) -> the result object of applyMaterialize plus the
+ *      text of every log (ptx_result_text_range): text: Uint16Array, textOff: BigUint64Array [nLogs + 1], textStatus: Uint32Array [nLogs], spanUnit: Uint32Array
+ *      (beside spanOff), textKernelMs ---- */
+ptx_dstrings* strings_of(napi_env env, napi_value v) {
+    void* p = nullptr;
+    if (napi_get_value_external(env, v, &p) != napi_ok) return nullptr;
+    return (ptx_dstrings*)p;
+}
+/* the arrays of a ptx_text as properties of `obj`; the text is freed here */
+static void text_to_js(napi_env env, ptx_text& t, napi_value obj) {
+    const size_t nl = (size_t)t.n_logs;
+    napi_value v = make_u32(env, t.status, nl);
+    if (v) napi_set_named_property(env, obj, "textStatus", v);
+    v = make_typed(env, napi_biguint64_array, 8, t.text_off, nl + 1);
+    if (v) napi_set_named_property(env, obj, "textOff", v);
+    v = make_typed(env, napi_uint16_array, 2, t.text, (size_t)t.text_off[nl]);
+    if (v) napi_set_named_property(env, obj, "text", v);
+    v = make_u32(env, t.span_unit, (size_t)t.span_off[nl]);
+    if (v) napi_set_named_property(env, obj, "spanUnit", v);
+    if (napi_create_double(env, (double)t.kernel_ms, &v) == napi_ok) napi_set_named_property(env, obj, "textKernelMs", v);
+    L.text_free(&t);
+}
+napi_value StringsUpload(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    if (!ctx) return throw_msg(env, "stringsUpload(ctx, units: Uint16Array, off: BigUint64Array)");
+    napi_typedarray_type tu, to;
+    size_t nu = 0, no = 0, offset = 0;
+    void *units = nullptr, *off = nullptr;
+    napi_value ab;
+    bool is_u = false, is_o = false;
+    napi_is_typedarray(env, argv[1], &is_u);
+    napi_is_typedarray(env, argv[2], &is_o);
+    if (!is_u || !is_o || napi_get_typedarray_info(env, argv[1], &tu, &nu, &units, &ab, &offset) != napi_ok || napi_get_typedarray_info(env, argv[2], &to, &no, &off, &ab, &offset) != napi_ok ||
+        tu != napi_uint16_array || to != napi_biguint64_array || no < 1 || no - 1 > 0xFFFFFFFFull || ((const uint64_t*)off)[no - 1] != nu)
+        return throw_msg(env, "stringsUpload: units must be a Uint16Array and off a BigUint64Array of n + 1 offsets that end at its length");
+    ptx_dstrings* ds = nullptr;
+    const ptx_status st = L.strings_upload(ctx, (const uint16_t*)units, (const uint64_t*)off, (uint32_t)(no - 1), &ds);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_strings_upload", st);
+    napi_value ext;
+    NAPI_OK(napi_create_external(env, ds, nullptr, nullptr, &ext));
+    return ext;
+}
+napi_value StringsFree(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 1 ? ctx_of(env, argv[0]) : nullptr;
+    ptx_dstrings* ds = ctx ? strings_of(env, argv[1]) : nullptr;
+    if (ds && L.handle) L.strings_free(ctx, ds);
+    return nullptr;
+}
+napi_value ResultText(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    ptx_dstrings* ds = ctx ? strings_of(env, argv[2]) : nullptr;
+    if (!ds) return throw_msg(env, "resultText(ctx, batch, strings)");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    ptx_dbatch* db = nullptr;
+    ptx_dresult* dr = nullptr;
+    ptx_result res;
+    ptx_text text;
+    bool have_res = false;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.result_alloc(ctx, db, &dr);
+    if (st == PTX_OK) st = L.merge(ctx, db, dr);
+    if (st == PTX_OK) st = L.result_download(ctx, db, dr, &res);
+    have_res = st == PTX_OK;
+    if (st == PTX_OK) st = L.result_text_range(ctx, db, dr, ds, 0, pb.n_logs, &text);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (dr) L.dresult_free(ctx, dr);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) {
+        if (have_res) L.result_free(&res);
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "resultText (ptx_merge / ptx_result_text_range) failed (status %d): %s", st, err.c_str());
+        return throw_msg(env, msg);
+    }
+    napi_value out = result_to_js(env, res, nullptr);
+    if (out) text_to_js(env, text, out);
+    else L.text_free(&text);
+    return out;
+}
+
 uint32_t u32_prop(napi_env env, napi_value obj, const char* name, uint32_t dflt) {
     napi_value v;
     bool has = false;
@@ -777,6 +875,15 @@ napi_value BatchAtVersions(napi_env env, napi_callback_info info) {
     const size_t na = pb.max_actors;
     if ((clocks && n_clocks != n * na) || (prefix && n_prefix != n)) return throw_msg(env, "batchAtVersions: clocks holds maxActors entries per cut, prefix one");
     const bool diff = u32_prop(env, argv[2], "diff", 0u) != 0u, then_rest = diff || u32_prop(env, argv[2], "thenRest", 0u) != 0u;
+    /* strings (optional): a stringsUpload handle — the text of the cut logs comes back with their result, as resultText returns it */
+    ptx_dstrings* ds = nullptr;
+    {
+        napi_value sv;
+        bool has = false;
+        if (napi_has_named_property(env, argv[2], "strings", &has) == napi_ok && has && napi_get_named_property(env, argv[2], "strings", &sv) == napi_ok) ds = strings_of(env, sv);
+    }
+    ptx_text text;
+    memset(&text, 0, sizeof(text));
     std::vector<uint32_t> out((5 + na) * n + 1, 0); /* status | nKept | firstRow | clocksOut */
     uint32_t none = 0; /* (a zero-length ArrayBuffer may come without storage) */
     ptx_dbatch *db = nullptr, *cut = nullptr;
@@ -797,6 +904,7 @@ napi_value BatchAtVersions(napi_env env, napi_callback_info info) {
     if (st == PTX_OK) st = L.sync(ctx);
     if (st == PTX_OK) st = L.result_download(ctx, cut, dr, &res);
     have_res = st == PTX_OK;
+    if (st == PTX_OK && ds) st = L.result_text_range(ctx, cut, dr, ds, 0, (uint32_t)n, &text);
     if (st == PTX_OK && diff) st = L.replay_patches_from(ctx, cut, dr, out.data() + 2 * n, &pat);
     std::string err = st != PTX_OK ? L.last_error(ctx) : "";
     if (dr) L.dresult_free(ctx, dr);
@@ -804,6 +912,7 @@ napi_value BatchAtVersions(napi_env env, napi_callback_info info) {
     if (db) L.batch_free(ctx, db);
     if (st != PTX_OK) {
         if (have_res) L.result_free(&res);
+        if (text.owner) L.text_free(&text);
         if (hb.owner) L.host_batch_free(&hb);
         char msg[1024];
         snprintf(msg, sizeof(msg), "ptx_batch_at_versions failed (status %d): %s", st, err.c_str());
@@ -812,6 +921,10 @@ napi_value BatchAtVersions(napi_env env, napi_callback_info info) {
     napi_value o, v, batch = batch_to_js(env, hb.b);
     L.host_batch_free(&hb);
     napi_value result = result_to_js(env, res, diff ? &pat : nullptr);
+    if (text.owner) {
+        if (result) text_to_js(env, text, result);
+        else L.text_free(&text);
+    }
     if (!batch || !result || napi_create_object(env, &o) != napi_ok) return throw_msg(env, "batchAtVersions: cannot build the result object");
     napi_set_named_property(env, o, "batch", batch);
     napi_set_named_property(env, o, "result", result);
@@ -1108,7 +1221,10 @@ napi_value Init(napi_env env, napi_value exports) {
     const napi_property_descriptor later[] = {{"syncReplicas", nullptr, SyncReplicas, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"accumulatePatches", nullptr, AccumulatePatches, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"checkPatches", nullptr, CheckPatches, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"batchAtVersions", nullptr, BatchAtVersions, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"batchAtVersions", nullptr, BatchAtVersions, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"stringsUpload", nullptr, StringsUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"stringsFree", nullptr, StringsFree, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"resultText", nullptr, ResultText, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

@@ -120,7 +120,7 @@ export class MergeEngine {
     /** docs -> replica logs -> changes in application order  =>  spans per replica log */
     /** without opts: the spans of the list under "text" per replica; with opts.listKeys (several list objects per document, round 5): every replica's entry is
      *  {key: getTextWithFormatting([key])} for the root keys named */
-    applyChanges(docs: Change[][][], opts?: { listKeys: string[] }): FormatSpanWithText[][][] | Array<Array<{ [key: string]: FormatSpanWithText[] }>>
+    applyChanges(docs: Change[][][], opts?: { listKeys?: string[]; text?: "device" | "host" }): FormatSpanWithText[][][] | Array<Array<{ [key: string]: FormatSpanWithText[] }>>
     /** spans as applyChanges + patches[doc][replica][change] = what applyChange(change) returns (micromerge.ts:499) */
     applyChangesWithPatches(docs: Change[][][]): { spans: FormatSpanWithText[][][]; patches: Patch[][][][] }
     /** patch streams (patchOff / patchLogs / patches of `res`: this library's, or a peer's) back into the documents they describe (ptx_accumulate_patches) */
@@ -145,7 +145,7 @@ export class MergeEngine {
     syncMany(docs: Change[][][], pairs: Array<{ doc: number; from: number; to: number }>, opts?: { maxAttempts?: number }): { changes: Change[][]; status: number[] }
     /** documents at past versions, many cuts in one call (ptx_batch_at_versions): per cut the spans at the version, its effective clock and — opts.diff — the Patch[] from there to the replica's present;
      *  a clock no replica could have had is status 3 with spans null */
-    documentsAt(docs: Change[][][], cuts: Array<{ doc: number; replica: number; clock: Record<ActorId, number> }> | Array<{ doc: number; replica: number; changes: number }>, opts?: { diff?: boolean }): Array<{ status: number; clock: Record<ActorId, number>; spans: FormatSpanWithText[] | null; patches?: Patch[] | null }>
+    documentsAt(docs: Change[][][], cuts: Array<{ doc: number; replica: number; clock: Record<ActorId, number> }> | Array<{ doc: number; replica: number; changes: number }>, opts?: { diff?: boolean; text?: "device" | "host" }): Array<{ status: number; clock: Record<ActorId, number>; spans: FormatSpanWithText[] | null; patches?: Patch[] | null }>
     replica(docId?: number | string, actorId?: ActorId): ReplicaHandle
     flush(wantPatches?: boolean): void
 }

@@ -519,6 +519,23 @@ function census(batch) {
     return hdr
 }
 
+/** the marks of one span row: attr word + the comment intervals that cover its first element */
+function spanMarks(batch, res, attr, start, bc, nCints, comments) {
+    const marks = {}
+    if (attr & ATTR.STRONG) marks.strong = { active: true }
+    if (attr & ATTR.EM) marks.em = { active: true }
+    if ((attr & ATTR.COMMENT) !== 0) {
+        const ids = []
+        for (let c = 0; c < nCints; c++) {
+            const id = res.cintervals[3 * (bc + c)], s = res.cintervals[3 * (bc + c) + 1], e = res.cintervals[3 * (bc + c) + 2]
+            if (s <= start && start < e) ids.push(id)
+        }
+        marks.comment = ids.map(i => comments[i]).sort().map(id => ({ id })) /* by id string (= by rank, unless the table grew in arrival order) */
+    }
+    if (attr & ATTR.LINK) marks.link = { url: batch.urls[attr & ATTR.ID_MASK] }
+    return marks
+}
+
 /** FormatSpanWithText[] of one log (what getTextWithFormatting(["text"]) returns, peritext.ts:337-395). */
 function decodeSpans(batch, res, log) {
     const r = res.logs.subarray(12 * log, 12 * log + 12)
@@ -532,21 +549,44 @@ function decodeSpans(batch, res, log) {
     for (let k = 0; k < nSpans; k++) {
         const start = res.spans[2 * (bs + k)], attr = res.spans[2 * (bs + k) + 1]
         const end = k + 1 < nSpans ? res.spans[2 * (bs + k + 1)] : nVisible
-        const marks = {}
-        if (attr & ATTR.STRONG) marks.strong = { active: true }
-        if (attr & ATTR.EM) marks.em = { active: true }
-        if ((attr & ATTR.COMMENT) !== 0) {
-            const ids = []
-            for (let c = 0; c < nCints; c++) {
-                const id = res.cintervals[3 * (bc + c)], s = res.cintervals[3 * (bc + c) + 1], e = res.cintervals[3 * (bc + c) + 2]
-                if (s <= start && start < e) ids.push(id)
-            }
-            marks.comment = ids.map(i => comments[i]).sort().map(id => ({ id })) /* by id string (= by rank, unless the table grew in arrival order) */
-        }
-        if (attr & ATTR.LINK) marks.link = { url: batch.urls[attr & ATTR.ID_MASK] }
+        const marks = spanMarks(batch, res, attr, start, bc, nCints, comments)
         let text = ""
         for (let q = start; q < end; q++) text += batch.values[res.values[bv + q]]
         out.push({ text, marks })
+    }
+    return out
+}
+
+/** The string table of a batch as ptx_strings_upload takes it: the UTF-16 code units of all strings back to back (a JS string IS its code units: lone
+ *  surrogates stay) and n + 1 offsets. */
+function encodeStrings(values) {
+    const off = new BigUint64Array(values.length + 1)
+    let n = 0
+    for (let i = 0; i < values.length; i++) {
+        n += values[i].length
+        off[i + 1] = BigInt(n)
+    }
+    const units = new Uint16Array(n)
+    let at = 0
+    for (const v of values) for (let k = 0; k < v.length; k++) units[at++] = v.charCodeAt(k)
+    return { units, off }
+}
+
+/** decodeSpans for a result that carries the text assembled on the device (addon.resultText: text / textOff / textStatus / spanUnit beside the compact rows):
+ *  the log's text is built ONCE from the UTF-16 buffer and every span's text is one slice of it between spanUnit values. */
+function decodeSpansText(batch, res, log) {
+    const r = res.logs.subarray(12 * log, 12 * log + 12)
+    const st = r[0] || res.textStatus[log]
+    if (st !== 0) throw new RangeError(STATUS_MESSAGES[st] || "merge error " + st)
+    const bs = Number(res.spanOff[log]), bc = Number(res.cintOff[log]), nSpans = r[4], nCints = r[5]
+    const t0 = Number(res.textOff[log]), t1 = Number(res.textOff[log + 1])
+    const whole = Buffer.from(res.text.buffer, res.text.byteOffset + 2 * t0, 2 * (t1 - t0)).toString("utf16le")
+    const comments = batch.docComments[batch.logDoc[log]]
+    const out = []
+    for (let k = 0; k < nSpans; k++) {
+        const start = res.spans[2 * (bs + k)], attr = res.spans[2 * (bs + k) + 1]
+        const text = whole.slice(res.spanUnit[bs + k], k + 1 < nSpans ? res.spanUnit[bs + k + 1] : t1 - t0)
+        out.push({ text, marks: spanMarks(batch, res, attr, start, bc, nCints, comments) })
     }
     return out
 }
@@ -821,14 +861,33 @@ class MergeEngine {
     applyChanges(docs, opts) {
         const listKeys = opts && opts.listKeys
         const batch = encodeDocs(docs, listKeys ? { listKeys } : undefined)
-        const res = this.applyMaterialize(batch)
+        const onDevice = this._textOnDevice(opts)
+        const res = onDevice ? this._withStrings(batch, strings => this.addon.resultText(this.ctx, batch, strings)) : this.applyMaterialize(batch)
+        const decode = onDevice ? decodeSpansText : decodeSpans
         let log = 0
-        if (!listKeys) return docs.map(logs => logs.map(() => decodeSpans(batch, res, log++)))
+        if (!listKeys) return docs.map(logs => logs.map(() => decode(batch, res, log++)))
         return docs.map(logs => logs.map(() => {
             const out = {}
-            for (const k of listKeys) out[k] = decodeSpans(batch, res, log++)
+            for (const k of listKeys) out[k] = decode(batch, res, log++)
             return out
         }))
+    }
+    /** opts.text: "device" = every log's text is assembled on the device (ptx_result_text_range) and a span's text is one slice of it; absent / "host" = the
+     *  string-table lookup per visible element */
+    _textOnDevice(opts) {
+        const t = opts && opts.text
+        if (t !== undefined && t !== "device" && t !== "host") throw new TypeError('text: "device" or "host"')
+        return t === "device"
+    }
+    /** the string table of an encoded batch made resident for the calls of `fn`: uploaded once per batch, freed with it */
+    _withStrings(batch, fn) {
+        const { units, off } = encodeStrings(batch.values)
+        const strings = this.addon.stringsUpload(this.ctx, units, off)
+        try {
+            return fn(strings)
+        } finally {
+            this.addon.stringsFree(this.ctx, strings)
+        }
     }
     /** Per-document digests (2 x u64 as BigInt pairs) of every log: equal digests <=> deep-equal spans. */
     digests(docs) {
@@ -959,7 +1018,9 @@ class MergeEngine {
             })
         } else arg.prefix = Uint32Array.from(cuts, c => Math.min(c.changes, VERSION_ALL))
         const tables = { values: batch.values, urls: batch.urls, logDoc: Array.from(src, l => batch.logDoc[l]), docActors: batch.docActors, docComments: batch.docComments, keys: batch.keys, mapValues: batch.mapValues }
-        const raw = this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 0 }, arg))
+        const onDevice = this._textOnDevice(opts)
+        const raw = onDevice ? this._withStrings(batch, strings => this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 0, strings }, arg)))
+                             : this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 0 }, arg))
         const cut = unpackEnvelope(Object.assign(raw.batch, tables))
         /* diff: a second call whose logs are the kept changes followed by the rest, replayed from the kept rows on */
         const rawDiff = diff ? this.addon.batchAtVersions(this.ctx, batch, Object.assign({ diff: 1 }, arg)) : null
@@ -970,7 +1031,7 @@ class MergeEngine {
             if (diff) out.patches = null
             if (status !== 0) return out
             for (let a = 0; a < actors.length; a++) if (raw.clocksOut[k * na + a]) out.clock[actors[a]] = raw.clocksOut[k * na + a]
-            if (Number(cut.logOff[k + 1]) > Number(cut.logOff[k])) out.spans = decodeSpans(cut, raw.result, k) /* (a version without any op holds no text list yet) */
+            if (Number(cut.logOff[k + 1]) > Number(cut.logOff[k])) out.spans = (onDevice ? decodeSpansText : decodeSpans)(cut, raw.result, k) /* (a version without any op holds no text list yet) */
             if (diff) out.patches = [].concat(...decodePatches(whole, rawDiff.result, k).slice(rawDiff.nKept[k]))
             return out
         })
@@ -1305,4 +1366,4 @@ class MergeEngine {
     }
 }
 
-module.exports = { MergeEngine, encodeDocs, encodeInputOps, packEnvelope, unpackEnvelope, decodeSpans, decodePatches, decodeChanges, decodeRoot, MAPV, prosemirrorDocFromSpans, PATCH, census, ACT, IN, MARK_NAMES, SIDE_NAMES, ATTR, STATUS_MESSAGES, ROOT, HEAD, VERSION_ALL }
+module.exports = { MergeEngine, encodeDocs, encodeInputOps, packEnvelope, unpackEnvelope, decodeSpans, decodeSpansText, decodePatches, decodeChanges, decodeRoot, MAPV, prosemirrorDocFromSpans, PATCH, census, ACT, IN, MARK_NAMES, SIDE_NAMES, ATTR, STATUS_MESSAGES, ROOT, HEAD, VERSION_ALL }

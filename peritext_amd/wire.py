@@ -780,6 +780,44 @@ def _marks_of_attr(batch, attr, comment_ids, comments):
     return marks
 
 
+@dataclass
+class Text:
+    """Host view of ptx_text (Engine.text): the text of a range of logs as ONE UTF-16 buffer.  Log l's code units are text[text_off[l] : text_off[l + 1]];
+    span k of log l starts at unit span_unit[span_off[l] + k] of the log's text and ends where span k + 1 starts (the last at the log's length)."""
+
+    status: np.ndarray  # u32 [n_logs] 0, the log's merge status, ERR_BAD_OP (a value id beyond the string table), ERR_CAPACITY
+    text_off: np.ndarray  # u64 [n_logs + 1]
+    text: np.ndarray  # u16 [text_off[n_logs]]
+    span_off: np.ndarray  # u64 [n_logs + 1]
+    span_unit: np.ndarray  # u32 [span_off[n_logs]]
+    kernel_ms: float = 0.0
+
+    def of_log(self, log):
+        """The text of one log as a str (JS string semantics: lone surrogates stay)."""
+        return self.text[int(self.text_off[log]) : int(self.text_off[log + 1])].astype("<u2").tobytes().decode("utf-16-le", "surrogatepass")
+
+
+def decode_spans_text(batch, res, text, log):
+    """decode_spans with the text assembled on the device: the same FormatSpanWithText[], every span's text ONE slice of the log's text between span_unit
+    values instead of a string-table lookup per element.  `res` and `text` cover the same range of logs.  A surrogate pair split over two spans stays
+    two lone surrogates, as in JS."""
+    r = res.logs[log]
+    st = int(r["status"]) or int(text.status[log])
+    if st != 0:
+        raise ValueError(abi.STATUS_NAMES.get(st, "error %d" % st))
+    _, s, c = canonical_of_log(batch, res, log)
+    comments = batch.doc_comments[batch.log_doc[log]]
+    t0, t1, k0 = int(text.text_off[log]), int(text.text_off[log + 1]), int(text.span_off[log])
+    units = text.text[t0:t1].astype("<u2")
+    cut = [int(x) for x in text.span_unit[k0 : k0 + len(s)]] + [t1 - t0]
+    out = []
+    for k in range(len(s)):
+        start, attr = int(s[k]["start"]), int(s[k]["attr"])
+        ids = [int(ci["id"]) for ci in c if int(ci["start"]) <= start < int(ci["end"])] if attr & abi.ATTR_COMMENT else []
+        out.append({"text": units[cut[k] : cut[k + 1]].tobytes().decode("utf-16-le", "surrogatepass"), "marks": _marks_of_attr(batch, attr, ids, comments)})
+    return out
+
+
 def decode_patches(batch, pat, log, with_rows=False):
     """Patch[] of one log in application order, in the reference's shapes (reference/src/micromerge.ts:214-222 Patch,
     :661-671 insert, :696-703 delete, src/peritext.ts:251-281 add/removeMark).  The makeList patch (the op itself,
