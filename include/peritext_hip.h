@@ -672,6 +672,48 @@ typedef struct ptx_text {
 ptx_status ptx_result_text_range(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, ptx_text* out);
 void ptx_text_free(ptx_text* t);
 
+/* ---- find in the documents' text without downloading it ----
+ * The reference has no search: its documents are JS strings (getTextWithFormatting, peritext.ts:337-395) and a caller writes text.indexOf(pattern, from).  This
+ * is String.prototype.indexOf applied repeatedly from p + 1, over the text ptx_result_text_range would return for the same range, which stays on the device:
+ *   match              a position p with 0 <= p <= L - m and text[p + i] == pattern[i] for all i < m (L: the log's text length in code units, m = n_pattern)
+ *   overlapping        ALL such positions are reported, overlapping ones included: "aaaa" holds "aa" three times
+ *   code units         the comparison is over UTF-16 code units, not code points: a pattern that is a lone high surrogate matches the first half of a pair, a
+ *                      pair split over two elements matches a two-unit pattern
+ *   PTX_FIND_ASCII_NOCASE   'A'..'Z' compare equal to 'a'..'z', in text and pattern; no other unit is folded (U+0130, U+212A match neither i nor k)
+ *   order and the cap  hit_unit ascends within a log; the listed hits are the FIRST max_hits_per_log of them; n_matches always counts all of them
+ *   count only         max_hits_per_log == 0: empty hit arrays — "which documents mention it"
+ *   log boundaries     a match never reaches from one log's text into the next log's
+ *   element mapping    element e holds unit u iff pre[e] <= u < pre[e + 1], pre = the exclusive scan of the elements' string lengths.  hit_start = the visible
+ *                      index of the element that holds the match's first unit, hit_end = that of its last unit + 1 — exclusive, as changeMark's endIndex
+ *                      (peritext.ts:491-497): delete {index: hit_start, count: hit_end - hit_start} and addMark {startIndex: hit_start, endIndex: hit_end} take
+ *                      them as they are, ptx_resolve_cursors (PTX_CURSOR_GET) turns them into elemIds.  An element whose string is empty holds no unit: it is
+ *                      never a hit_start, but may lie inside [hit_start, hit_end).  A match inside one multi-unit element (a pasted paragraph inserted as one
+ *                      value) has hit_end == hit_start + 1; hit_unit tells where it sits
+ *   per-log status     exactly ptx_text.status of the same range, under the same guarantee (every value id is checked before anything is read through it): the
+ *                      log's merge status, PTX_ERR_BAD_OP for a value id >= n_strings, PTX_ERR_CAPACITY.  A log that is not PTX_OK has zero matches; the other
+ *                      logs are untouched
+ * PTX_ERR_INVALID_ARG: n_pattern == 0, n_pattern > PTX_FIND_PATTERN_MAX, an unknown flag bit, a range outside the batch.  n_logs == 0 returns an empty result
+ * (hit_off = {0}).  `pattern` is a HOST pointer, copied before the call returns.  elem_rank is not needed (PTX_FLAG_NO_ELEM_RANK contexts work).  Synchronises. */
+#define PTX_FIND_PATTERN_MAX 256u      /* code units */
+#define PTX_FIND_ASCII_NOCASE 1u
+typedef struct ptx_matches {
+    uint32_t n_logs;
+    uint32_t n_pattern;
+    float kernel_ms;               /* HIP events around every launch of the call */
+    uint32_t reserved;
+    const uint32_t* status;        /* [n_logs] exactly ptx_text.status of the same range */
+    const uint32_t* n_matches;     /* [n_logs] ALL matches of the log, listed or not */
+    const uint64_t* hit_off;       /* [n_logs + 1] listed hits: min(n_matches[l], max_hits_per_log) per log */
+    const uint32_t* hit_unit;      /* [hit_off[n_logs]] code-unit offset of the match within the log's text, ascending per log */
+    const uint32_t* hit_start;     /* ... visible index of the element that holds the match's first unit */
+    const uint32_t* hit_end;       /* ... visible index of the element that holds its last unit, + 1 */
+    void* owner;
+} ptx_matches;
+/* Owned by the library until ptx_matches_free. */
+ptx_status ptx_result_find_text(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs,
+                                const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, ptx_matches* out);
+void ptx_matches_free(ptx_matches* m);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

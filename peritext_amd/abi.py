@@ -275,6 +275,28 @@ class ptx_text(C.Structure):
     ]
 
 
+# find in the documents' text (ptx_result_find_text; peritext_amd/csrc/find_core.h)
+FIND_STEP = 256  # PTX_FIND_STEP: candidate positions per step of the walk
+FIND_PATTERN_MAX = 256  # PTX_FIND_PATTERN_MAX: code units
+FIND_ASCII_NOCASE = 1  # PTX_FIND_ASCII_NOCASE
+
+
+class ptx_matches(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("n_pattern", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("reserved", C.c_uint32),
+        ("status", u32p),
+        ("n_matches", u32p),
+        ("hit_off", u64p),
+        ("hit_unit", u32p),
+        ("hit_start", u32p),
+        ("hit_end", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
 # numpy dtypes with the same layout
 import numpy as np  # noqa: E402
 
@@ -366,6 +388,8 @@ FUNCTIONS = {
     "ptx_strings_free": (None, [vp, vp]),
     "ptx_result_text_range": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(ptx_text)]),
     "ptx_text_free": (None, [C.POINTER(ptx_text)]),
+    "ptx_result_find_text": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_matches)]),
+    "ptx_matches_free": (None, [C.POINTER(ptx_matches)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

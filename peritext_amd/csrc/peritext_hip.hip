@@ -38,6 +38,7 @@
 #include "version_core.h"
 #include "accum_core.h"
 #include "text_core.h"
+#include "find_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -592,6 +593,47 @@ extern "C" __global__ void __launch_bounds__(1024) ptx_text_offsets_kernel(uint6
 extern "C" __global__ void __launch_bounds__(64) ptx_text_assemble_kernel(PtxTextArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t ptx_text_lds[PTX_TEXT_LDS_BYTES];
     if (blockIdx.x < A.n_logs) ptx_text_assemble_log<64>(A, blockIdx.x, ptx_text_lds);
+}
+
+/* ---- find in the assembled text (find_core.h): one wave per log counts the matches; one workgroup scans min(count, cap) into hit_off (the twin of
+ *      ptx_text_offsets_kernel, a chunk of 1 024 logs per step); one wave per log lists its first hits in order and maps them to elements ---- */
+extern "C" __global__ void __launch_bounds__(64) ptx_find_count_kernel(PtxFindArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_find_lds[PTX_FIND_LDS_BYTES];
+    if (blockIdx.x < A.T.n_logs) ptx_find_count_log<64>(A, blockIdx.x, ptx_find_lds);
+}
+extern "C" __global__ void __launch_bounds__(1024) ptx_find_offsets_kernel(const uint32_t* n_matches, uint32_t cap, uint64_t* hit_off /* [n_logs + 1] */, uint32_t n_logs) {
+    __shared__ uint64_t wsum[16];
+    __shared__ uint64_t run;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) run = 0;
+    __syncthreads();
+    for (uint32_t c0 = 0; c0 < n_logs; c0 += 1024u) {
+        const uint32_t l = c0 + threadIdx.x;
+        uint64_t v = 0;
+        if (l < n_logs) v = n_matches[l] < cap ? n_matches[l] : cap;
+        uint64_t x = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t y = __shfl_up(x, d, 64);
+            if ((int)lane >= d) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint64_t base = run;
+        for (uint32_t w = 0; w < wave; ++w) base += wsum[w];
+        if (l < n_logs) hit_off[l] = base + x - v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t t = 0;
+            for (uint32_t w = 0; w < 16u; ++w) t += wsum[w];
+            run += t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) hit_off[n_logs] = run;
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_find_emit_kernel(PtxFindArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_find_lds[PTX_FIND_LDS_BYTES];
+    if (blockIdx.x < A.T.n_logs) ptx_find_emit_log<64>(A, blockIdx.x, ptx_find_lds);
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -2208,6 +2250,144 @@ ptx_status ptx_result_text_range(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dr
     out->span_off = offs + no;
     out->text = (const uint16_t*)hp1;
     out->span_unit = (const uint32_t*)(hp1 + tx_bytes);
+    out->owner = h;
+    return PTX_OK;
+}
+
+/* ---- find in the assembled text (find_core.h): the text passes above into a pool block that is never downloaded, then count, scan, emit.  Three waits: the text's
+ *      size, the number of listed hits, the hits (a count-only call, or one without a hit, has two) ---- */
+void ptx_matches_free(ptx_matches* m) {
+    if (!m) return;
+    delete (ptx_host_result*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+ptx_status ptx_result_find_text(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, const uint16_t* pattern,
+                                uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, ptx_matches* out) {
+    if (!ctx || !b || !r || !s || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    if (!pattern || n_pattern == 0) return fail(ctx, PTX_ERR_INVALID_ARG, "empty pattern");
+    if (n_pattern > PTX_FIND_PATTERN_MAX) return fail(ctx, PTX_ERR_INVALID_ARG, "pattern longer than PTX_FIND_PATTERN_MAX code units");
+    if (flags & ~PTX_FIND_ASCII_NOCASE) return fail(ctx, PTX_ERR_INVALID_ARG, "unknown find flag");
+    if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
+    if ((uint64_t)first_log + n_logs > r->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "log range exceeds the result");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_host_result* h = new ptx_host_result();
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status | n_matches | hit_off — what comes down — | the text passes' two offset rows | the pattern */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), down0 = 2 * st_bytes + a16(no * 8), off_at = down0, pat_at = off_at + a16(2 * no * 8), blk0 = pat_at + a16((uint64_t)n_pattern * 2);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, blk0);
+    uint64_t* hit_off = (uint64_t*)(hp0 + 2 * st_bytes);
+    uint64_t* totals = (uint64_t*)(hp0 + off_at); /* [0] code units, [1] spans of the range */
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t tu = 0, ts = 0, nhits = 0;
+    PtxFindArgs A;
+    memset(&A, 0, sizeof(A));
+    if (e == hipSuccess) {
+        A.T.log_off = b->log_off;
+        A.T.logs = r->logs;
+        A.T.values = r->values;
+        A.T.spans = r->spans;
+        A.T.units = s->units;
+        A.T.str_off = s->off;
+        A.T.n_strings = s->n;
+        A.T.first_log = first_log;
+        A.T.n_logs = n_logs;
+        A.T.status = (uint32_t*)d0;
+        A.T.off = (uint64_t*)(d0 + off_at);
+        A.n_matches = (uint32_t*)(d0 + st_bytes);
+        A.hit_off = (uint64_t*)(d0 + 2 * st_bytes);
+        A.pattern = (const uint16_t*)(d0 + pat_at);
+        A.n_pattern = n_pattern;
+        A.flags = flags;
+        A.cap = max_hits_per_log;
+        memcpy(hp0 + pat_at, pattern, (size_t)n_pattern * 2); /* the caller's pattern is free to go */
+        hit_off[0] = 0;                                       /* an empty range: hit_off = {0} */
+    }
+    if (e == hipSuccess && n_logs) {
+        e = hipMemcpyAsync(d0 + pat_at, hp0 + pat_at, (size_t)n_pattern * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_length_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.T.off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&totals[0], A.T.off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&totals[1], A.T.off + no + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) {
+            tu = totals[0];
+            ts = totals[1];
+            if (ts > r->n_rows) e = hipErrorInvalidValue; /* (a log never produces more rows than it has ops) */
+        }
+    }
+    /* block 1, device only: the text and the spans' unit offsets (scratch: the assemble pass writes them, nobody reads them) */
+    const uint64_t tx_bytes = a16(tu * 2), blk1 = tx_bytes + a16(ts * 4) + 16;
+    if (e == hipSuccess && n_logs) {
+        e = ptx_dev_malloc((void**)&d1, blk1);
+        if (e == hipSuccess) {
+            A.T.text = (uint16_t*)d1;
+            A.T.span_unit = (uint32_t*)(d1 + tx_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_assemble_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+            hipLaunchKernelGGL(ptx_find_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)A.n_matches, max_hits_per_log, A.hit_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0, d0, down0, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nhits = hit_off[n_logs];
+    }
+    /* block 2, device and pinned host alike: hit_unit | hit_start | hit_end */
+    const uint64_t col = a16(nhits * 4), blk2 = 3 * col + 16;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    if (e == hipSuccess && nhits) {
+        e = ptx_dev_malloc((void**)&d2, blk2);
+        if (e == hipSuccess) {
+            A.hit_unit = (uint32_t*)d2;
+            A.hit_start = (uint32_t*)(d2 + col);
+            A.hit_end = (uint32_t*)(d2 + 2 * col);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_find_emit_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp1, d2, 3 * col, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
+    }
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    (void)ptx_dev_free(d2);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("find text: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->n_pattern = n_pattern;
+    out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->status = (const uint32_t*)hp0;
+    out->n_matches = (const uint32_t*)(hp0 + st_bytes);
+    out->hit_off = hit_off;
+    out->hit_unit = (const uint32_t*)hp1;
+    out->hit_start = (const uint32_t*)(hp1 + col);
+    out->hit_end = (const uint32_t*)(hp1 + 2 * col);
     out->owner = h;
     return PTX_OK;
 }

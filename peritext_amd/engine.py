@@ -63,6 +63,13 @@ def _copy_result(res):
     )
 
 
+def _copied(ptr, dtype, count):
+    """A numpy copy of `count` items of a library-owned array (the library frees its own right after)."""
+    if count == 0:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+
+
 class Engine:
     """One device context (one HIP stream).  One Engine per process/GPU in multi-GPU runs."""
 
@@ -339,18 +346,32 @@ class Engine:
         t = abi.ptx_text()
         self._check(self.lib.ptx_result_text_range(self.ctx, dbatch, dresult, dstrings, first_log, n_logs, C.byref(t)))
         try:
-            n = int(t.n_logs)
-
-            def arr(ptr, dtype, count):
-                if count == 0:
-                    return np.zeros(0, dtype=dtype)
-                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
-
+            n, arr = int(t.n_logs), _copied
             text_off, span_off = arr(t.text_off, np.uint64, n + 1), arr(t.span_off, np.uint64, n + 1)
             return wire.Text(status=arr(t.status, np.uint32, n), text_off=text_off, text=arr(t.text, np.uint16, int(text_off[n])), span_off=span_off,
                              span_unit=arr(t.span_unit, np.uint32, int(span_off[n])), kernel_ms=float(t.kernel_ms))
         finally:
             self.lib.ptx_text_free(C.byref(t))
+
+    def find_text(self, dbatch, dresult, dstrings, pattern, first_log=0, n_logs=None, ascii_nocase=False, max_hits_per_log=0xFFFFFFFF):
+        """Every position of `pattern` (a str: UTF-16 code units, lone surrogates allowed) in the text of the logs [first_log, first_log + n_logs), found on the
+        device without downloading the text (ptx_result_find_text): wire.Matches — per log the count of ALL matches and, for the first max_hits_per_log of
+        them in ascending order, the code-unit offset and the range [hit_start, hit_end) of visible element indexes, which Engine.change takes as
+        delete {index, count} or addMark {startIndex, endIndex}.  max_hits_per_log=0 only counts."""
+        if n_logs is None:
+            n_logs = self.n_logs(dbatch) - first_log
+        pat = np.frombuffer(pattern.encode("utf-16-le", "surrogatepass"), dtype="<u2").astype(np.uint16)
+        m = abi.ptx_matches()
+        self._check(self.lib.ptx_result_find_text(self.ctx, dbatch, dresult, dstrings, first_log, n_logs, pat.ctypes.data_as(abi.u16p), len(pat),
+                                                  abi.FIND_ASCII_NOCASE if ascii_nocase else 0, max_hits_per_log, C.byref(m)))
+        try:
+            n, arr = int(m.n_logs), _copied
+            hit_off = arr(m.hit_off, np.uint64, n + 1)
+            nh = int(hit_off[n])
+            return wire.Matches(status=arr(m.status, np.uint32, n), n_matches=arr(m.n_matches, np.uint32, n), hit_off=hit_off, hit_unit=arr(m.hit_unit, np.uint32, nh),
+                                hit_start=arr(m.hit_start, np.uint32, nh), hit_end=arr(m.hit_end, np.uint32, nh), n_pattern=int(m.n_pattern), kernel_ms=float(m.kernel_ms))
+        finally:
+            self.lib.ptx_matches_free(C.byref(m))
 
     def replay_patches(self, dbatch, dresult, first_row=None):
         """The Patch[] stream every applyChange of every log would have returned (reference/src/micromerge.ts:499),

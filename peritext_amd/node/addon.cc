@@ -89,6 +89,9 @@ struct Lib {
     void (*strings_free)(ptx_ctx*, ptx_dstrings*) = nullptr;
     ptx_status (*result_text_range)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, ptx_text*) = nullptr;
     void (*text_free)(ptx_text*) = nullptr;
+    /* find in that text without downloading it */
+    ptx_status (*result_find_text)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, const uint16_t*, uint32_t, uint32_t, uint32_t, ptx_matches*) = nullptr;
+    void (*matches_free)(ptx_matches*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -138,7 +141,8 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.device_read, "ptx_device_read") && sym(L.resolve_cursors, "ptx_resolve_cursors") && sym(L.batch_append_device, "ptx_batch_append_device") &&
                   sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches") &&
                   sym(L.batch_at_versions, "ptx_batch_at_versions") && sym(L.strings_upload, "ptx_strings_upload") && sym(L.strings_free, "ptx_strings_free") &&
-                  sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free");
+                  sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free") && sym(L.result_find_text, "ptx_result_find_text") &&
+                  sym(L.matches_free, "ptx_matches_free");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -610,6 +614,60 @@ napi_value ResultText(napi_env env, napi_callback_info info) {
     napi_value out = result_to_js(env, res, nullptr);
     if (out) text_to_js(env, text, out);
     else L.text_free(&text);
+    return out;
+}
+
+/* ---- find in the documents' text without downloading it (INTEGRATION.md "Find without downloading the text"): findText(ctx, batch, strings, pattern:
+ *      Uint16Array, flags, maxHitsPerLog) uploads, merges and searches in one call (ptx_result_find_text) -> {status: Uint32Array [nLogs], nMatches: Uint32Array
+ *      [nLogs], hitOff: BigUint64Array [nLogs + 1], hitUnit / hitStart / hitEnd: Uint32Array [hitOff[nLogs]], kernelMs} ---- */
+napi_value FindText(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 5 ? ctx_of(env, argv[0]) : nullptr;
+    ptx_dstrings* ds = ctx ? strings_of(env, argv[2]) : nullptr;
+    if (!ds) return throw_msg(env, "findText(ctx, batch, strings, pattern: Uint16Array, flags, maxHitsPerLog)");
+    napi_typedarray_type tp;
+    size_t np = 0, offset = 0;
+    void* pat = nullptr;
+    napi_value ab;
+    bool is_p = false;
+    napi_is_typedarray(env, argv[3], &is_p);
+    uint32_t flags = 0, cap = 0;
+    if (!is_p || napi_get_typedarray_info(env, argv[3], &tp, &np, &pat, &ab, &offset) != napi_ok || tp != napi_uint16_array || np > 0xFFFFFFFFull ||
+        napi_get_value_uint32(env, argv[4], &flags) != napi_ok || napi_get_value_uint32(env, argv[5], &cap) != napi_ok)
+        return throw_msg(env, "findText: pattern must be a Uint16Array, flags and maxHitsPerLog unsigned 32-bit numbers");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    const uint16_t none = 0; /* (a zero-length typed array may come without storage: the library answers n_pattern == 0 itself) */
+    ptx_dbatch* db = nullptr;
+    ptx_dresult* dr = nullptr;
+    ptx_matches m;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.result_alloc(ctx, db, &dr);
+    if (st == PTX_OK) st = L.merge(ctx, db, dr);
+    if (st == PTX_OK) st = L.result_find_text(ctx, db, dr, ds, 0, pb.n_logs, np ? (const uint16_t*)pat : &none, (uint32_t)np, flags, cap, &m);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (dr) L.dresult_free(ctx, dr);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) {
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "findText (ptx_merge / ptx_result_find_text) failed (status %d): %s", st, err.c_str());
+        return throw_msg(env, msg);
+    }
+    const size_t nl = (size_t)m.n_logs, nh = (size_t)m.hit_off[nl];
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        if ((v = make_u32(env, m.status, nl))) napi_set_named_property(env, out, "status", v);
+        if ((v = make_u32(env, m.n_matches, nl))) napi_set_named_property(env, out, "nMatches", v);
+        if ((v = make_typed(env, napi_biguint64_array, 8, m.hit_off, nl + 1))) napi_set_named_property(env, out, "hitOff", v);
+        if ((v = make_u32(env, m.hit_unit, nh))) napi_set_named_property(env, out, "hitUnit", v);
+        if ((v = make_u32(env, m.hit_start, nh))) napi_set_named_property(env, out, "hitStart", v);
+        if ((v = make_u32(env, m.hit_end, nh))) napi_set_named_property(env, out, "hitEnd", v);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.matches_free(&m);
     return out;
 }
 
@@ -1224,7 +1282,8 @@ napi_value Init(napi_env env, napi_value exports) {
                                               {"batchAtVersions", nullptr, BatchAtVersions, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"stringsUpload", nullptr, StringsUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"stringsFree", nullptr, StringsFree, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"resultText", nullptr, ResultText, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"resultText", nullptr, ResultText, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"findText", nullptr, FindText, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

@@ -121,6 +121,9 @@ export class MergeEngine {
     /** without opts: the spans of the list under "text" per replica; with opts.listKeys (several list objects per document, round 5): every replica's entry is
      *  {key: getTextWithFormatting([key])} for the root keys named */
     applyChanges(docs: Change[][][], opts?: { listKeys?: string[]; text?: "device" | "host" }): FormatSpanWithText[][][] | Array<Array<{ [key: string]: FormatSpanWithText[] }>>
+    /** every position of `needle` in every replica's text, found on the device without downloading the text (ptx_result_find_text): indexOf repeated from p + 1 over UTF-16
+     *  code units; count = all matches, hits = the first opts.maxHits (default: all), ascending; [startIndex, endIndex) is the visible element range change() takes */
+    findText(docs: Change[][][], needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number }): Array<Array<{ status: number; count: number; hits: Array<{ unit: number; startIndex: number; endIndex: number }> }>>
     /** spans as applyChanges + patches[doc][replica][change] = what applyChange(change) returns (micromerge.ts:499) */
     applyChangesWithPatches(docs: Change[][][]): { spans: FormatSpanWithText[][][]; patches: Patch[][][][] }
     /** patch streams (patchOff / patchLogs / patches of `res`: this library's, or a peer's) back into the documents they describe (ptx_accumulate_patches) */

@@ -40,6 +40,8 @@ const IN = { INSERT: 0, DELETE: 1, ADDMARK: 2, REMOVEMARK: 3, MAKELIST: 4, MAPSE
 const IN_OBJ_NEW = 0x80000000 /* ptx_input_ops.index of a map op: the object made by row k of this log's output */ /* ptx_input_ops.action */
 const CHG_ACTOR_SHIFT = 20, CHG_NOPS = 0x000fffff, ENV_SATURATED = 65535
 const VERSION_ALL = 0xffffffff /* PTX_VERSION_ALL: a clock entry that keeps every change of the actor */
+const FIND_PATTERN_MAX = 256 /* PTX_FIND_PATTERN_MAX: code units of a needle */
+const FIND_ASCII_NOCASE = 1 /* PTX_FIND_ASCII_NOCASE */
 const envStride = maxActors => (1 + maxActors + 3) & ~3 /* PTX_ENV_STRIDE */
 
 /** chgActor / chgSeq / chgNops / chgDeps -> the packed envelope the device reads: chgHdr = actor << 20 | nops, chgEnv rows of
@@ -888,6 +890,27 @@ class MergeEngine {
         } finally {
             this.addon.stringsFree(this.ctx, strings)
         }
+    }
+    /** Every position of `needle` in the text of every replica, found on the device without downloading the text (ptx_result_find_text): encode, upload, merge
+     *  and find in one call.  The semantics are String.prototype.indexOf repeated from p + 1 over UTF-16 code units (overlapping matches included).  Per document
+     *  and replica { status, count, hits }: count = ALL matches, hits = the first opts.maxHits of them (default: all) in ascending order, each { unit: code-unit
+     *  offset in the replica's text, startIndex, endIndex: the visible element range, the end exclusive — what change() takes as addMark { startIndex, endIndex }
+     *  or delete { index: startIndex, count: endIndex - startIndex } }.  opts.ignoreAsciiCase: 'A'..'Z' equal 'a'..'z', nothing else is folded.  A replica
+     *  whose merge failed has its status and no hits. */
+    findText(docs, needle, opts) {
+        if (typeof needle !== "string" || needle.length === 0 || needle.length > FIND_PATTERN_MAX) throw new RangeError("needle: a string of 1 .. " + FIND_PATTERN_MAX + " UTF-16 code units")
+        const maxHits = opts && opts.maxHits !== undefined ? opts.maxHits : 0xFFFFFFFF
+        if (!Number.isInteger(maxHits) || maxHits < 0 || maxHits > 0xFFFFFFFF) throw new RangeError("maxHits: an unsigned 32-bit integer")
+        const pattern = new Uint16Array(needle.length) /* code units, not code points: a lone surrogate is a legal needle */
+        for (let i = 0; i < needle.length; i++) pattern[i] = needle.charCodeAt(i)
+        const batch = encodeDocs(docs)
+        const m = this._withStrings(batch, strings => this.addon.findText(this.ctx, batch, strings, pattern, opts && opts.ignoreAsciiCase ? FIND_ASCII_NOCASE : 0, maxHits))
+        let log = 0
+        return docs.map(logs => logs.map(() => {
+            const l = log++, hits = []
+            for (let k = Number(m.hitOff[l]); k < Number(m.hitOff[l + 1]); k++) hits.push({ unit: m.hitUnit[k], startIndex: m.hitStart[k], endIndex: m.hitEnd[k] })
+            return { status: m.status[l], count: m.nMatches[l], hits }
+        }))
     }
     /** Per-document digests (2 x u64 as BigInt pairs) of every log: equal digests <=> deep-equal spans. */
     digests(docs) {

@@ -797,6 +797,26 @@ class Text:
         return self.text[int(self.text_off[log]) : int(self.text_off[log + 1])].astype("<u2").tobytes().decode("utf-16-le", "surrogatepass")
 
 
+@dataclass
+class Matches:
+    """Host view of ptx_matches (Engine.find_text): n_matches[l] counts ALL matches of log l; its listed hits — the first max_hits_per_log, ascending — are the
+    rows hit_off[l] .. hit_off[l + 1] of hit_unit (code-unit offset within the log's text), hit_start and hit_end (visible element indexes, the end exclusive)."""
+
+    status: np.ndarray  # u32 [n_logs] exactly Text.status of the same range
+    n_matches: np.ndarray  # u32 [n_logs]
+    hit_off: np.ndarray  # u64 [n_logs + 1]
+    hit_unit: np.ndarray  # u32 [hit_off[n_logs]]
+    hit_start: np.ndarray  # u32 ...
+    hit_end: np.ndarray  # u32 ...
+    n_pattern: int = 0
+    kernel_ms: float = 0.0
+
+    def of_log(self, log):
+        """[(unit, start_index, end_index)] of one log's listed hits."""
+        a, b = int(self.hit_off[log]), int(self.hit_off[log + 1])
+        return [(int(self.hit_unit[k]), int(self.hit_start[k]), int(self.hit_end[k])) for k in range(a, b)]
+
+
 def decode_spans_text(batch, res, text, log):
     """decode_spans with the text assembled on the device: the same FormatSpanWithText[], every span's text ONE slice of the log's text between span_unit
     values instead of a string-table lookup per element.  `res` and `text` cover the same range of logs.  A surrogate pair split over two spans stays
