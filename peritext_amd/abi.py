@@ -255,6 +255,10 @@ class ptx_host_batch(C.Structure):
     _fields_ = [("b", ptx_batch), ("owner", C.c_void_p)]
 
 
+# the merge kernel's last phase (LWW winners, spans; peritext_amd/csrc/merge_core.h)
+LWW_TILE_4 = 128  # PTX_TILE_4: visible chars up to which the four LWW trees are resident at once (twice that with a tree per present type)
+LWW_TILE_1 = 512  # PTX_TILE_1: tile of the visible axis for longer documents (twice that where the launch's LDS window has room)
+
 # document text (ptx_result_text_range; peritext_amd/csrc/text_core.h)
 TEXT_TILE = 256  # PTX_TEXT_TILE: visible elements per step of the assemble walk
 TEXT_LANE_MAX = 16  # PTX_TEXT_LANE_MAX: a value of more code units than this is copied by the whole wave
