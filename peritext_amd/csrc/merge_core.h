@@ -73,6 +73,9 @@
 #ifndef PTX_UM
 #define PTX_UM 1u /* mark ops per thread and step in P5a: five gathers per op, so one op in flight + one in work */
 #endif
+#ifndef PTX_MARK_OPS_FORM
+#define PTX_MARK_OPS_FORM 1 /* which bodies hold P5a's second form, the one that reads a resident log's operand words (an expression over the body's template parameters; 0: the gathers alone) */
+#endif
 #ifndef PTX_UB64
 #define PTX_UB64 1u
 #endif
@@ -165,6 +168,10 @@ struct PtxMergeArgs {
     uint32_t* row_index_bits; /* with it: the add / remove bitmaps of the logs' mark ops */
     uint32_t* rows_indexed;   /* with it [n_logs]: N once the log's index stands, else 0 */
     uint32_t row_index_write;
+    /* the operand words of the mark ops (see ptx_mark_operand_pack below), handed out with the row index or not at all: both nullptr = P5a gathers every op's
+     * operands through its row, as before.  The launch that writes the index writes them; a launch that reads the index reads those of the logs whose word stands */
+    uint64_t* mark_ops;       /* optional: one word per mark op, log l from word ptx_row_index_off(row offset, l) */
+    uint32_t* mark_ops_stand; /* with it [n_logs]: N once the operand words of all the log's mark ops stand, else 0 */
 };
 
 /* ---- the row index of one log of a resident batch: what the row pass P1 has derived from op_id / action / mark_type and the log's header, columns that no entry
@@ -366,16 +373,35 @@ PTX_DEV int ptx_elem_lookup(const PtxElemIndex& ix, uint64_t id) {
 /* The same for the logs this file's kernel takes (max_counter < 2^19 and max_actor < 4096 were checked against the header: every factor fits 24 bits): the key
  * by ONE full-rate v_mad_u32_u24 — the compiler's own choice for `ctr * na1 + actor` is the quarter-rate 64-bit multiply-add —, an id outside the header's bounds
  * looks up key 0 (a counter of 0: no insert of an accepted log has it), and no branch: one 8-byte LDS read, a select at the end. */
-PTX_DEV int ptx_elem_lookup24(const PtxElemIndex& ix, uint64_t id) {
+PTX_DEV uint32_t ptx_id_key24(const PtxElemIndex& ix, uint64_t id) {
     const uint32_t ctr = (uint32_t)(id >> 32), actor = (uint32_t)id;
     const bool ok = (ctr - 1u < ix.max_ctr) & (actor <= ix.max_actor);
     const uint32_t key0 = ptx_mul24(ctr, ix.na1) + actor; /* (not the inline-asm form: the compiler branches around an asm it cannot speculate) */
-    const uint32_t key = ok ? key0 : 0u;
+    return ok ? key0 : 0u;
+}
+/* (key: inside the keyspace) */
+PTX_DEV int ptx_key_lookup(const PtxElemIndex& ix, uint32_t key) {
     const PtxBitWord w = ix.ib[key >> 5];
     const uint32_t s = key & 31u;
     const uint32_t r = w.pre + ptx_popc(w.bits & ((1u << s) - 1u));
     return ((w.bits >> s) & 1u) ? (int)r : -1;
 }
+PTX_DEV int ptx_elem_lookup24(const PtxElemIndex& ix, uint64_t id) { return ptx_key_lookup(ix, ptx_id_key24(ix, id)); }
+
+/* ---- the operand word of a mark op of an indexed log: what P5a derives from ref_a / ref_b / side_a / side_b / payload of the op's row and the log's header,
+ *      columns that no entry point may modify (16-bit id keys: only such logs have an index).  Low half: key of ref_a | key of ref_b << 16, each what
+ *      ptx_id_key24 answers (0 = an id outside the header's bounds).  High half: the comment id (comment ops: the payload if below the header's n_comment_ids,
+ *      else 0; other ops: 0) | class of side_a << 16 | class of side_b << 18 (0 before, 1 after, 2 anything else) | "a comment op whose payload is not
+ *      below n_comment_ids" << 20.  Word k of a log belongs to entry k of its mark park. ---- */
+PTX_HD uint32_t ptx_side_class(uint32_t side) { return side <= PTX_SIDE_AFTER ? side : 2u; }
+PTX_HD uint64_t ptx_mark_operand_pack(uint32_t key_a, uint32_t key_b, uint32_t side_a, uint32_t side_b, uint32_t comment_id, bool bad_comment) {
+    const uint32_t hi = (comment_id & 0xFFFFu) | (ptx_side_class(side_a) << 16) | (ptx_side_class(side_b) << 18) | (bad_comment ? 1u << 20 : 0u);
+    return (uint64_t)((key_a & 0xFFFFu) | (key_b << 16)) | ((uint64_t)hi << 32);
+}
+/* P5a gathers the operands of one mark op through its row: counted by the CPU test-suite's driver of the operand words, nothing anywhere else */
+#ifndef PTX_NOTE_MARK_GATHER
+#define PTX_NOTE_MARK_GATHER() ((void)0)
+#endif
 
 /* ---- LDS bump allocator ---- */
 struct PtxBump {
@@ -1619,6 +1645,11 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         }                                                                                    \
     } while (0)
     PTX_IDX_PARK_IF(PTX_FRESH_ARGS(A), kIdx && idx_on);
+    /* The operand words of the log's mark ops (ptx_mark_operand_pack).  The launch that writes the index stores them from P5a's registers and lets their word
+     * stand behind its loop; a launch that reads the index and finds that word standing runs P5a on them (no gather through the rows).  The word is stored by a
+     * launch that also stored rows_indexed — further up in the same kernel — and a reader sees either only after that whole kernel: it stands => the index stands. */
+    constexpr bool kOps = kIdx && PTX_MARK_OPS_FORM;
+    const bool ops_rd = kOps && idx_read && PTX_FRESH_ARGS(A).mark_ops && PTX_CONST_LOAD(&PTX_FRESH_ARGS(A).mark_ops_stand[log]) == N;
     uint16_t* klist = L;
     uint16_t* bigp = ptx_alloc<uint16_t>(bp, n / (PTX_SMALL_BUCKET + 1u) + 2); /* parents with more than PTX_SMALL_BUCKET children */
     /* parents with two or more children (at most half of the elements' parents); once they are sorted the same words hold the bitmap that ranks a huge bucket */
@@ -1990,7 +2021,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
 #define PTX_MARK_OF(st_, u_, k_) ptx_mark_of(MB, PTX_JB_BLOCK(st_, u_, PTX_UM), PTX_JB_LANE(st_, u_, PTX_UM), k_)
 #endif
     uint32_t kq[PTX_UM], kq_n[PTX_UM]; /* the thread's mark ops of a step (0xFFFFFFFF: none) */
-    uint32_t mq[PTX_UM];               /* the park entries of the step whose gathers go out next */
+    uint32_t mq[PTX_UM] = {};          /* the park entries of the step whose gathers go out next */
 #define PTX_MARK_PQ(st_, mq_)                                               \
     _Pragma("unroll") for (int u = 0; u < (int)PTX_UM; ++u) {               \
         uint32_t k_;                                                        \
@@ -2011,12 +2042,24 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         pl_[u] = has_ && k_ >= moff2 && k_ < moff3 ? 1u : 0u;               \
     }                                                                       \
     _Pragma("unroll") for (int u = 0; u < (int)PTX_UM; ++u) {               \
+        PTX_NOTE_MARK_GATHER();                                             \
         rb_[u] = ref_b[i_[u]];                                              \
         ra_[u] = PTX_KO_P5A_RA ? rb_[u] : ref_a[i_[u]];                     \
         sa_[u] = side_a[i_[u]];                                             \
         sb_[u] = side_b[i_[u]];                                             \
         if (pl_[u]) pl_[u] = payload[i_[u]];                                \
     }
+    /* the second form (ops_rd): the park word and the operand word of the thread's mark ops of a step, two independent loads by k, nothing behind them (a lane
+     * without an op loads word 0 of both; the words are read-only for this launch: plain loads).  pw_: the park words, ow_: the operand words */
+#define PTX_MARK_LOAD_OPS(st_, kq_, pw_, ow_, opw_)                         \
+    _Pragma("unroll") for (int u = 0; u < (int)PTX_UM; ++u) {               \
+        uint32_t k_;                                                        \
+        const bool has_ = PTX_MARK_OF(st_, u, k_);                         \
+        kq_[u] = has_ ? k_ : 0xFFFFFFFFu;                                   \
+        pw_[u] = park[K ? mp0 + k_ : 0u];                                   \
+        ow_[u] = (opw_)[k_];                                                \
+    }
+#define PTX_MARK_OPW(F_) ((const uint64_t*)F_.mark_ops + ptx_row_index_off(base, log))
     /* ---- P3: causal tree of the inserts -> document position of every element ---- */
     {
         /* children per parent -> bucket starts -> bucket ends; 16-bit counters, two per atomically updated word */
@@ -2163,7 +2206,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         PTX_BAIL_IF_ERROR();
         PTX_STAMP(3);
         PTX_REMAT_AT(3, PTX_REMAT_P3());
-        PTX_MARK_PQ(0u, mq) /* P5a's first park entries: on their way while the tree is ordered and ranked (LDS only) */
+        if (!(kOps && ops_rd)) { PTX_MARK_PQ(0u, mq) } /* P5a's first park entries: on their way while the tree is ordered and ranked (LDS only); the second form has no stage behind them and loads them with its operand words, ahead of P4 */
         /* P3c: the children of every parent in descending element index == descending opId (the skip loop of micromerge.ts:630-635), one PARENT per lane.
          * Pass 1, all parents: an only child (most elements are one) is placed at once, a parent with more goes to a list.  Pass 2, the listed parents: a
          * bucket of up to PTX_SMALL_BUCKET members is sorted in registers by a 19-exchange network; up to PTX_HUGE_BUCKET members by PTX_G lanes per member,
@@ -2416,8 +2459,13 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
 #endif
 
     /* (P5a's loads: the park entries of its first step went out at the start of P3c) their gathers go out here, ahead of P4, and the second step's park entries */
-    PTX_MARK_LOAD(0u, kq, i, ra, rb, sa, sb, pl, mq)
-    PTX_MARK_PQ(1u, mq)
+    if (kOps && ops_rd) { /* (the second form: the first step's two loads go out here; ra holds a step's operand words, i its park words) */
+        const uint64_t* const opw = PTX_MARK_OPW(PTX_FRESH_ARGS(A));
+        PTX_MARK_LOAD_OPS(0u, kq, i, ra, opw)
+    } else {
+        PTX_MARK_LOAD(0u, kq, i, ra, rb, sa, sb, pl, mq)
+        PTX_MARK_PQ(1u, mq)
+    }
     /* ---- P4: tombstones -> visible index ---- */
     const uint32_t nwv = nwe; /* bit positions 0..n by document position */
     alive = ptx_alloc<PtxBitWord>(bp, nwv + 1);
@@ -2519,26 +2567,23 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
     PTX_STAMP(13); /* the values are out; the marks' intervals follow */
     PTX_REMAT_AT(9, PTX_REMAT());
     {
-    /* two register sets in turn (no copies from "next" to "current"): kq / i / ra ... hold the even steps' mark ops, the *_n set the odd ones' */
-    auto mark_step = [&](const uint32_t (&kq)[PTX_UM], const uint32_t (&i)[PTX_UM], const uint64_t (&ra)[PTX_UM], const uint64_t (&rb)[PTX_UM], const uint32_t (&sa)[PTX_UM],
-                         const uint32_t (&sb)[PTX_UM], const uint32_t (&pl)[PTX_UM]) {
-#pragma unroll
-        for (int u = 0; u < (int)PTX_UM; ++u)
-            if (kq[u] != 0xFFFFFFFFu) {
-                const uint32_t k = kq[u];
+    /* One mark op behind its two look-ups, the piece both forms of the loop share.  row: the op's row; js0 / je0: the elements of its start and end (-1: none);
+     * sa / sb: the sides as the columns hold them or as their classes (ptx_side_class: the tests below cannot tell the two apart); cm: the comment id of a
+     * comment op, bad_cm: that id is not below the header's n_comment_ids. */
+    auto mark_tail = [&](const uint32_t k, const uint32_t row, const int js0, const int je0, const uint32_t sa, const uint32_t sb, const uint32_t cm,
+                         const bool bad_cm) __attribute__((always_inline)) {
                 /* Both boundaries side by side, no branch: the two chains id -> element -> (row, position) -> visible rank are three dependent LDS round trips
                  * together (written as nested ifs they were eight, one after the other: round 6 found the kernel bound by its chain of fixed latencies, not by
                  * instruction issue).  start: only before/after(elem) can ever match a slot (peritext.ts:236); an element that is not in the list when the op
                  * is applied means the op never starts; an end that is not found is never reached: the mark runs to the end of the text. */
-                const int js0 = ptx_elem_lookup24(ix, ra[u]), je0 = ptx_elem_lookup24(ix, rb[u]);
                 const uint32_t ea = js0 < 0 ? 0u : (uint32_t)js0, eb = je0 < 0 ? 0u : (uint32_t)je0;
                 const uint32_t row_a = row_of[ea], row_b = row_of[eb], rk_a = rnk[ea];
                 uint32_t rk_b = rnk[eb];
                 PTX_KEEP_VGPR(rk_b); /* (read now, with the other three: left alone the compiler sinks this read behind the test of the end's row) */
-                const bool has_a = (sa[u] <= PTX_SIDE_AFTER) & (js0 >= 0) & (row_a < i[u]); /* (& not &&: a short-circuit puts the LDS reads back into branches) */
-                const bool has_b = (sb[u] <= PTX_SIDE_AFTER) & (je0 >= 0) & (row_b < i[u]);
-                const uint32_t slot_a = 2u * rk_a + (sa[u] == PTX_SIDE_AFTER ? 1u : 0u);
-                uint32_t slot_b = has_b ? 2u * rk_b + (sb[u] == PTX_SIDE_AFTER ? 1u : 0u) : 0xFFFFFFFFu;
+                const bool has_a = (sa <= PTX_SIDE_AFTER) & (js0 >= 0) & (row_a < row); /* (& not &&: a short-circuit puts the LDS reads back into branches) */
+                const bool has_b = (sb <= PTX_SIDE_AFTER) & (je0 >= 0) & (row_b < row);
+                const uint32_t slot_a = 2u * rk_a + (sa == PTX_SIDE_AFTER ? 1u : 0u);
+                uint32_t slot_b = has_b ? 2u * rk_b + (sb == PTX_SIDE_AFTER ? 1u : 0u) : 0xFFFFFFFFu;
                 /* same slot: the start test fires first and the end is never seen */
                 if (slot_b == slot_a) slot_b = 0xFFFFFFFFu;
                 const bool covers = has_a & (slot_b > slot_a);
@@ -2553,17 +2598,53 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
                 if (out_refs) {
                     /* both boundary slots, each on its own (the replay needs the end slot even where the op never starts) */
                     uint32_t va = 0xFFFFu, vb = 0xFFFFu;
-                    if (js >= 0) va = 2u * rnk[js] + (sa[u] == PTX_SIDE_AFTER ? 1u : 0u);
-                    if (sb[u] == PTX_SIDE_BEFORE || sb[u] == PTX_SIDE_AFTER) {
-                        const int je = ptx_elem_lookup24(ix, rb[u]);
-                        if (je >= 0 && row_of[je] < i[u]) vb = 2u * rnk[je] + (sb[u] == PTX_SIDE_AFTER ? 1u : 0u);
+                    if (js >= 0) va = 2u * rnk[js] + (sa == PTX_SIDE_AFTER ? 1u : 0u);
+                    if (sb <= PTX_SIDE_AFTER) {
+                        if (je0 >= 0 && row_of[je0] < row) vb = 2u * rnk[je0] + (sb == PTX_SIDE_AFTER ? 1u : 0u);
                     }
-                    out_refs[base + i[u]] = va | (vb << 16);
+                    out_refs[base + row] = va | (vb << 16);
                 }
                 if (k >= moff2 && k < moff3) {
-                    if (pl[u] >= Kid) ptx_raise(H, i[u], 1, PTX_ERR_BAD_OP); /* beyond the id space the header declares */
-                    cid[k - moff2] = (uint16_t)(pl[u] < Kid ? pl[u] : 0u);
+                    if (bad_cm) ptx_raise(H, row, 1, PTX_ERR_BAD_OP); /* beyond the id space the header declares */
+                    cid[k - moff2] = (uint16_t)(cm < Kid ? cm : 0u);
                 }
+    };
+    if (kOps && ops_rd) {
+        /* The second form: the operand words of a resident log's mark ops stand (ptx_mark_operand_pack).  One step ahead of the step in work go two loads by k, the
+         * park word for the row and the operand word — no stage behind them, no gather, one evaluation of the lane's share per step.  "As if it came from the
+         * rows": every key is clamped to the keyspace, every row to the log, the comment id as in the first form. */
+        const uint64_t* const opw = PTX_MARK_OPW(PTX_FRESH_ARGS(A));
+#pragma nounroll
+        for (uint32_t st = 0; st < m_steps; ++st) {
+            PTX_MARK_LOAD_OPS(st + 1u, kq_n, i_n, ra_n, opw)
+#pragma unroll
+            for (int u = 0; u < (int)PTX_UM; ++u)
+                if (kq[u] != 0xFFFFFFFFu) {
+                    const uint32_t r = i[u] & 0xFFFFu, w0 = (uint32_t)ra[u], w1 = (uint32_t)(ra[u] >> 32);
+                    const uint32_t ka = w0 & 0xFFFFu, kb = w0 >> 16;
+                    mark_tail(kq[u], r < N ? r : N - 1u, ptx_key_lookup(ix, ka < keyspace ? ka : keyspace - 1u), ptx_key_lookup(ix, kb < keyspace ? kb : keyspace - 1u),
+                              (w1 >> 16) & 3u, (w1 >> 18) & 3u, w1 & 0xFFFFu, ((w1 >> 20) & 1u) != 0u);
+                }
+#pragma unroll
+            for (int u = 0; u < (int)PTX_UM; ++u) kq[u] = kq_n[u], i[u] = i_n[u], ra[u] = ra_n[u];
+        }
+    } else {
+    /* The first form.  The launch that writes the log's index stores every op's operand word on its way (a plain store by k that nothing in this kernel waits
+     * for; a lane's ops of a block are consecutive k) and lets the log's word stand behind the loop: who reads either does so in a LATER kernel (launch_merge). */
+    uint64_t* const opw_w = kIdx && small_keys && PTX_FRESH_ARGS(A).row_index && PTX_FRESH_ARGS(A).row_index_write && PTX_FRESH_ARGS(A).mark_ops
+                                ? PTX_FRESH_ARGS(A).mark_ops + ptx_row_index_off(base, log) : nullptr;
+    /* two register sets in turn (no copies from "next" to "current"): kq / i / ra ... hold the even steps' mark ops, the *_n set the odd ones' */
+    auto mark_step = [&](const uint32_t (&kq)[PTX_UM], const uint32_t (&i)[PTX_UM], const uint64_t (&ra)[PTX_UM], const uint64_t (&rb)[PTX_UM], const uint32_t (&sa)[PTX_UM],
+                         const uint32_t (&sb)[PTX_UM], const uint32_t (&pl)[PTX_UM]) {
+#pragma unroll
+        for (int u = 0; u < (int)PTX_UM; ++u)
+            if (kq[u] != 0xFFFFFFFFu) {
+                const uint32_t k = kq[u], ka = ptx_id_key24(ix, ra[u]), kb = ptx_id_key24(ix, rb[u]);
+                if (kIdx && opw_w) {
+                    const bool cmt = k >= moff2 && k < moff3;
+                    opw_w[k] = ptx_mark_operand_pack(ka, kb, sa[u], sb[u], cmt && pl[u] < Kid ? pl[u] : 0u, cmt && pl[u] >= Kid);
+                }
+                mark_tail(k, i[u], ptx_key_lookup(ix, ka), ptx_key_lookup(ix, kb), sa[u], sb[u], pl[u], pl[u] >= Kid);
             }
     };
 #pragma nounroll
@@ -2576,7 +2657,11 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         PTX_MARK_PQ(st + 3u, mq)
         mark_step(kq_n, i_n, ra_n, rb_n, sa_n, sb_n, pl_n);
     }
+    if (kIdx && opw_w) PTX_LEADER { PTX_FRESH_ARGS(A).mark_ops_stand[log] = N; }
+    }
 #undef PTX_MARK_LOAD
+#undef PTX_MARK_LOAD_OPS
+#undef PTX_MARK_OPW
 #undef PTX_MARK_PQ
 #undef PTX_MARK_OF
     }

@@ -795,6 +795,11 @@ struct ptx_dbatch {
      * has one; the big block is never zeroed (rows_indexed, one word per log, says which logs' regions hold anything).  Beside the marks the second thing a
      * merge writes into a batch.  Who writes and who may read is decided per launch (launch_merge) from the state below, under g_index_mu. */
     uint32_t *row_index = nullptr, *row_index_bits = nullptr, *rows_indexed = nullptr;
+    /* the operand words of the mark ops (merge_core.h ptx_mark_operand_pack): what P5a derives from ref_a / ref_b / side_a / side_b / payload of a mark op's row,
+     * 8 bytes per row of capacity at the index's own region offsets, and one word per log that says whether the log's words stand.  Made with the index or not
+     * at all, written by the index's one writer, read by its readers; neither block nullptr or both */
+    uint64_t* mark_ops = nullptr;
+    uint32_t* mark_ops_stand = nullptr;
     mutable int index_state = 0;               /* 0 nobody has written it; 1 a launch is being enqueued that writes it; 2 written by a launch of context index_writer on index_stream, index_ev recorded behind it; 3 that launch has ended */
     mutable uint64_t index_writer = 0;         /* ptx_ctx::serial of the writing context */
     mutable hipStream_t index_stream = nullptr;
@@ -834,7 +839,14 @@ struct ptx_dresult {
 };
 
 static std::mutex g_index_mu;                        /* the index_state / index_stream / index_ev of every batch */
+static void free_mark_ops(ptx_dbatch* b) {
+    (void)ptx_dev_free(b->mark_ops);
+    (void)ptx_dev_free(b->mark_ops_stand);
+    b->mark_ops = nullptr;
+    b->mark_ops_stand = nullptr;
+}
 static void free_row_index(ptx_dbatch* b) {
+    free_mark_ops(b);
     (void)ptx_dev_free(b->row_index);
     (void)ptx_dev_free(b->row_index_bits);
     (void)ptx_dev_free(b->rows_indexed);
@@ -1001,6 +1013,16 @@ static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr, b
         if (e == hipSuccess) e = ptx_dev_malloc((void**)&b->row_index, (size_t)ptx_row_index_words(b->n_ops, b->n_logs) * 4);
         if (e == hipSuccess) e = ptx_dev_malloc((void**)&b->row_index_bits, (size_t)ptx_row_bits_words(b->n_ops, b->n_logs) * 4);
         if (e == hipSuccess) e = hipMemsetAsync(b->rows_indexed, 0, (size_t)b->n_logs * 4, ctx->stream);
+        if (e == hipSuccess) {
+            /* the operand words: 8 bytes per row beside the index's ~4.1; a failed allocation leaves the batch with its index and without them, never with an error */
+            hipError_t eo = ptx_dev_malloc((void**)&b->mark_ops_stand, (size_t)b->n_logs * 4);
+            if (eo == hipSuccess) eo = ptx_dev_malloc((void**)&b->mark_ops, (size_t)ptx_row_index_words(b->n_ops, b->n_logs) * 8);
+            if (eo == hipSuccess) eo = hipMemsetAsync(b->mark_ops_stand, 0, (size_t)b->n_logs * 4, ctx->stream);
+            if (eo != hipSuccess) {
+                (void)hipGetLastError();
+                free_mark_ops(b);
+            }
+        }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->index_ev, hipEventDisableTiming); /* recorded behind the one merge that writes the index (launch_merge) */
         /* the zeroes stand before the batch is handed out: its first merge may come from another context, on a stream nothing orders behind this one */
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1571,6 +1593,8 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
     A.row_index_bits = idx_mode ? b->row_index_bits : nullptr;
     A.rows_indexed = idx_mode ? b->rows_indexed : nullptr;
     A.row_index_write = idx_mode == 1 ? 1u : 0u;
+    A.mark_ops = idx_mode ? b->mark_ops : nullptr; /* (with the index, under its protocol: its writer writes them, its readers read them) */
+    A.mark_ops_stand = idx_mode ? b->mark_ops_stand : nullptr;
     /* one workgroup per log; far more workgroups than the 256 CUs so the dispatcher load-balances.  Up to three launches (census_and_shape): the many at
      * their LDS window, the few that need a larger one, the logs beyond one CU's LDS through the HBM-staged kernel — the latter two on a side stream forked
      * from and joined to the caller's, so that they run beside the many instead of after them. */
@@ -1673,6 +1697,19 @@ int ptx_debug_row_index(ptx_ctx* ctx, const ptx_dbatch* b, uint32_t* n_indexed) 
         for (uint32_t v : h) *n_indexed += v != 0u;
     std::lock_guard<std::mutex> g(g_index_mu);
     return b->index_state;
+}
+
+/* Test hook beside ptx_debug_row_index, NOT part of the C ABI: *n_stand = the logs whose operand words stand (mark_ops_stand set), read after everything this
+ * context has enqueued.  Returns -1 for a batch without operand words, else 0. */
+int ptx_debug_mark_operands(ptx_ctx* ctx, const ptx_dbatch* b, uint32_t* n_stand) {
+    if (n_stand) *n_stand = 0;
+    if (!ctx || !b || !b->mark_ops || !b->mark_ops_stand) return -1;
+    if (ptx_enter(ctx) != hipSuccess) return -1;
+    std::vector<uint32_t> h(b->n_logs);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(h.data(), b->mark_ops_stand, (size_t)b->n_logs * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (n_stand)
+        for (uint32_t v : h) *n_stand += v != 0u;
+    return 0;
 }
 
 ptx_status ptx_merge_timed(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r, uint32_t iters, float* ms_total) {
