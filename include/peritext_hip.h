@@ -714,6 +714,49 @@ ptx_status ptx_result_find_text(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dre
                                 const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, ptx_matches* out);
 void ptx_matches_free(ptx_matches* m);
 
+/* ---- the text of element ranges, with their formatting, without downloading the documents ----
+ * The reference's caller slices what getTextWithFormatting returned; a hit of ptx_result_find_text, a comment interval (ptx_cinterval) and a span are ranges of
+ * visible ELEMENT indexes of a log.  This returns the text and the span rows of many such ranges of many logs in one call; the documents' text stays on the
+ * device.  Log l of the range has the slices slice_off[l] .. slice_off[l + 1] of slice_start / slice_end.
+ *   clamping           Array.prototype.slice(start, end) over the log's n_visible elements, for non-negative arguments: elem_end = min(end, n_visible),
+ *                      elem_start = min(start, n_visible); elem_start >= elem_end after that is the EMPTY slice, reported as elem_start == elem_end ==
+ *                      min(start, n_visible).  0xFFFFFFFF is a legal bound: a context window [hit_start - c, hit_end + c) needs no clamping by the caller
+ *                      beyond saturating the subtraction at 0
+ *   order              the slices of a log may come in any order, overlap, nest and repeat; every output follows the caller's order
+ *   text               slice k's code units are text[unit_off[k] .. unit_off[k + 1]) = the concatenation of string[values[i]] for i in [elem_start, elem_end).
+ *                      UTF-16 code units, as ptx_text: a slice that cuts a surrogate pair split over two elements returns a lone surrogate; an element whose
+ *                      string is empty contributes nothing but is still an element
+ *   span rows          slice k's rows are sspans / sspan_unit [sspan_off[k] .. sspan_off[k + 1]).  For a non-empty slice [a, b) they are the log's span rows with
+ *                      start < b whose successor's start (the last row's: n_visible) is > a, in order, `attr` unchanged; the first row's start is raised to a.
+ *                      `start` stays a DOCUMENT element index — the log's cintervals, addMark {startIndex} and cursor requests take it as it is;
+ *                      sspan_unit is the code-unit offset of that start within the SLICE's text.  A row ends where the next one starts, the last at elem_end.
+ *                      A slice made only of empty-string elements has zero units and still its rows.  An empty slice has zero rows.  Comment ids are not
+ *                      repeated: a row with PTX_ATTR_COMMENT is resolved against the log's cintervals, as for the full result
+ *   per-log status     exactly ptx_text.status of the same range, under the same guarantee (every value id is checked before anything is read through it).  A
+ *                      log that is not PTX_OK has empty slices without rows, elem_start == elem_end == 0; the other logs are untouched
+ * PTX_ERR_INVALID_ARG: a range outside the batch; slice_off[0] != 0 or a slice_off that decreases; slice_off == NULL with n_logs > 0; a NULL slice_start or
+ * slice_end with slices present; more than 0xFFFFFFFF slices.  n_logs == 0 or zero slices returns an empty result (unit_off = sspan_off = {0}).  The three
+ * slice arrays are HOST pointers, copied before the call returns.  elem_rank is not needed (PTX_FLAG_NO_ELEM_RANK contexts work).  Synchronises. */
+typedef struct ptx_slices {
+    uint32_t n_logs;
+    uint32_t n_slices;
+    float kernel_ms;               /* HIP events around every launch of the call, the text passes included */
+    uint32_t reserved;
+    const uint32_t* status;        /* [n_logs] exactly ptx_text.status of the same range */
+    const uint32_t* elem_start;    /* [n_slices] the range after clamping */
+    const uint32_t* elem_end;      /* ... */
+    const uint64_t* unit_off;      /* [n_slices + 1] code units */
+    const uint16_t* text;          /* [unit_off[n_slices]] the slices' text back to back, in the caller's order */
+    const uint64_t* sspan_off;     /* [n_slices + 1] rows of the two arrays below */
+    const ptx_span* sspans;        /* [sspan_off[n_slices]] start: a document element index, >= elem_start of its slice; attr: the log's row's */
+    const uint32_t* sspan_unit;    /* ... code-unit offset of `start` within the slice's text */
+    void* owner;
+} ptx_slices;
+/* Owned by the library until ptx_slices_free. */
+ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs,
+                                  const uint64_t* slice_off, const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out);
+void ptx_slices_free(ptx_slices* m);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

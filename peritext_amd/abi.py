@@ -301,6 +301,28 @@ class ptx_matches(C.Structure):
     ]
 
 
+# text and span rows of element ranges (ptx_result_text_slices; peritext_amd/csrc/slice_core.h)
+SLICE_BLOCK = 1024  # PTX_SLICE_BLOCK: code units of the output per wave of the copy pass
+
+
+class ptx_slices(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("n_slices", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("reserved", C.c_uint32),
+        ("status", u32p),
+        ("elem_start", u32p),
+        ("elem_end", u32p),
+        ("unit_off", u64p),
+        ("text", u16p),
+        ("sspan_off", u64p),
+        ("sspans", C.c_void_p),
+        ("sspan_unit", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
 # numpy dtypes with the same layout
 import numpy as np  # noqa: E402
 
@@ -394,6 +416,8 @@ FUNCTIONS = {
     "ptx_text_free": (None, [C.POINTER(ptx_text)]),
     "ptx_result_find_text": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_matches)]),
     "ptx_matches_free": (None, [C.POINTER(ptx_matches)]),
+    "ptx_result_text_slices": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, u64p, u32p, u32p, C.POINTER(ptx_slices)]),
+    "ptx_slices_free": (None, [C.POINTER(ptx_slices)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

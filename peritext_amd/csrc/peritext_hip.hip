@@ -39,6 +39,7 @@
 #include "accum_core.h"
 #include "text_core.h"
 #include "find_core.h"
+#include "slice_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -634,6 +635,30 @@ extern "C" __global__ void __launch_bounds__(1024) ptx_find_offsets_kernel(const
 extern "C" __global__ void __launch_bounds__(64) ptx_find_emit_kernel(PtxFindArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t ptx_find_lds[PTX_FIND_LDS_BYTES];
     if (blockIdx.x < A.T.n_logs) ptx_find_emit_log<64>(A, blockIdx.x, ptx_find_lds);
+}
+
+/* ---- text and span rows of element ranges (slice_core.h): a lane per log plans the prefix block; one wave per log that has a slice writes its element prefix;
+ *      a lane per slice clamps, measures and finds its span rows; ptx_text_offsets_kernel scans both counts; one wave per PTX_SLICE_BLOCK code units of OUTPUT
+ *      copies; a lane per output row emits the clipped spans ---- */
+extern "C" __global__ void __launch_bounds__(256) ptx_slice_plan_kernel(PtxSliceArgs A) {
+    const uint32_t l = blockIdx.x * 256u + threadIdx.x;
+    if (l < A.T.n_logs) ptx_slice_plan_one(A, l);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_slice_prefix_kernel(PtxSliceArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_slice_lds[PTX_SLICE_LDS_BYTES];
+    if (blockIdx.x < A.T.n_logs) ptx_slice_prefix_log<64>(A, blockIdx.x, ptx_slice_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_slice_bounds_kernel(PtxSliceArgs A) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < A.n_slices) ptx_slice_bounds_one(A, k); /* (the grid is ceil(n_slices / 256) <= 2^24 blocks: k does not wrap) */
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_slice_copy_kernel(PtxSliceArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_slice_lds[PTX_SLICE_LDS_BYTES];
+    ptx_slice_copy_block<64>(A, blockIdx.x, ptx_slice_lds); /* (a block behind the output's end returns at once) */
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_slice_span_kernel(PtxSliceArgs A, uint64_t n_rows) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r < n_rows) ptx_slice_span_one(A, r);
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -2425,6 +2450,179 @@ ptx_status ptx_result_find_text(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dre
     out->hit_unit = (const uint32_t*)hp1;
     out->hit_start = (const uint32_t*)(hp1 + col);
     out->hit_end = (const uint32_t*)(hp1 + 2 * col);
+    out->owner = h;
+    return PTX_OK;
+}
+
+/* ---- text and span rows of element ranges (slice_core.h): the text passes into a pool block that is never downloaded, then plan, prefix, bounds, scan, copy and
+ *      span emit.  Three waits: the sizes of the text and of the prefix block; the sizes of the output; the output (a call without slices has one) ---- */
+void ptx_slices_free(ptx_slices* m) {
+    if (!m) return;
+    delete (ptx_host_result*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, const uint64_t* slice_off,
+                                  const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out) {
+    if (!ctx || !b || !r || !s || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
+    if ((uint64_t)first_log + n_logs > r->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "log range exceeds the result");
+    if (n_logs && !slice_off) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off is NULL");
+    if (n_logs && slice_off[0] != 0) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off[0] is not 0");
+    for (uint32_t l = 0; l < n_logs; ++l)
+        if (slice_off[l + 1] < slice_off[l]) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off decreases");
+    const uint64_t ns64 = n_logs ? slice_off[n_logs] : 0;
+    if (ns64 > 0xFFFFFFFFull) return fail(ctx, PTX_ERR_INVALID_ARG, "more than 2^32 - 1 slices");
+    if (ns64 && (!slice_start || !slice_end)) return fail(ctx, PTX_ERR_INVALID_ARG, "slices present but slice_start or slice_end is NULL");
+    const uint32_t ns = (uint32_t)ns64;
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_host_result* h = new ptx_host_result();
+    const uint64_t no = (uint64_t)n_logs + 1, nso = ns64 + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status | elem_start | elem_end | unit_off, sspan_off — what comes down — | slice_off | slice_start | slice_end — what
+     * goes up — ; the device's goes on with the text passes' two offset rows | the plan's two | slice_log | first_span | src_off; the host's with three totals */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), col = a16(ns64 * 4), es_at = st_bytes, ee_at = es_at + col, oo_at = ee_at + col, down0 = oo_at + a16(2 * nso * 8);
+    const uint64_t so_at = down0, ss_at = so_at + a16(no * 8), se_at = ss_at + col, up_end = se_at + col;
+    const uint64_t hblk0 = up_end + 32;
+    const uint64_t off_at = up_end, po_at = off_at + a16(2 * no * 8), sl_at = po_at + a16(2 * no * 8), fs_at = sl_at + col, src_at = fs_at + col, dblk0 = src_at + a16(ns64 * 8);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, hblk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, dblk0);
+    uint64_t* out_off = (uint64_t*)(hp0 + oo_at);
+    uint64_t* totals = (uint64_t*)(hp0 + up_end); /* [0] code units, [1] spans of the range, [2] words of the prefix block */
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t tu = 0, ts = 0, tp = 0, out_units = 0, out_rows = 0;
+    PtxSliceArgs A;
+    memset(&A, 0, sizeof(A));
+    if (e == hipSuccess) {
+        A.T.log_off = b->log_off;
+        A.T.logs = r->logs;
+        A.T.values = r->values;
+        A.T.spans = r->spans;
+        A.T.units = s->units;
+        A.T.str_off = s->off;
+        A.T.n_strings = s->n;
+        A.T.first_log = first_log;
+        A.T.n_logs = n_logs;
+        A.T.status = (uint32_t*)d0;
+        A.T.off = (uint64_t*)(d0 + off_at);
+        A.slice_off = (const uint64_t*)(d0 + so_at);
+        A.slice_start = (const uint32_t*)(d0 + ss_at);
+        A.slice_end = (const uint32_t*)(d0 + se_at);
+        A.n_slices = ns;
+        A.pre_off = (uint64_t*)(d0 + po_at);
+        A.elem_start = (uint32_t*)(d0 + es_at);
+        A.elem_end = (uint32_t*)(d0 + ee_at);
+        A.out_off = (uint64_t*)(d0 + oo_at);
+        A.slice_log = (uint32_t*)(d0 + sl_at);
+        A.first_span = (uint32_t*)(d0 + fs_at);
+        A.src_off = (uint64_t*)(d0 + src_at);
+        /* the caller's arrays are free to go */
+        if (n_logs) memcpy(hp0 + so_at, slice_off, (size_t)no * 8);
+        if (ns) {
+            memcpy(hp0 + ss_at, slice_start, (size_t)ns * 4);
+            memcpy(hp0 + se_at, slice_end, (size_t)ns * 4);
+        }
+        out_off[0] = out_off[nso] = 0; /* no slices: unit_off = sspan_off = {0} */
+    }
+    if (e == hipSuccess && n_logs) {
+        e = hipMemcpyAsync(d0 + so_at, hp0 + so_at, up_end - so_at, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_length_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.T.off, n_logs);
+            if (ns) {
+                hipLaunchKernelGGL(ptx_slice_plan_kernel, dim3((n_logs + 255u) / 256u), dim3(256), 0, ctx->stream, A);
+                hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.pre_off, n_logs);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0, d0, (size_t)n_logs * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&totals[0], A.T.off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&totals[1], A.T.off + no + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && ns) e = hipMemcpyAsync(&totals[2], A.pre_off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) {
+            tu = totals[0];
+            ts = totals[1];
+            tp = ns ? totals[2] : 0;
+            if (ts > r->n_rows || tp > r->n_rows + n_logs) e = hipErrorInvalidValue; /* (a log never produces more rows than it has ops) */
+        }
+    }
+    /* block 1, device only: the text, the spans' unit offsets (the assemble pass writes them, nobody reads them) and the element prefixes */
+    const uint64_t tx_bytes = a16(tu * 2), su_bytes = a16(ts * 4), blk1 = tx_bytes + su_bytes + a16(tp * 4) + 16;
+    if (e == hipSuccess && ns) {
+        e = ptx_dev_malloc((void**)&d1, blk1);
+        if (e == hipSuccess) {
+            A.T.text = (uint16_t*)d1;
+            A.T.span_unit = (uint32_t*)(d1 + tx_bytes);
+            A.pre = (uint32_t*)(d1 + tx_bytes + su_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_text_assemble_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+            hipLaunchKernelGGL(ptx_slice_prefix_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_slice_bounds_kernel, dim3((uint32_t)((ns64 + 255) / 256)), dim3(256), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.out_off, ns);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + es_at, d0 + es_at, down0 - es_at, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) {
+            out_units = out_off[ns];
+            out_rows = out_off[nso + ns];
+        }
+    }
+    /* block 2, device and pinned host alike: text | sspans | sspan_unit */
+    const uint64_t ot_bytes = a16(out_units * 2), os_bytes = a16(out_rows * sizeof(ptx_span)), blk2 = ot_bytes + os_bytes + a16(out_rows * 4) + 16;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    if (e == hipSuccess && (out_units || out_rows)) {
+        e = ptx_dev_malloc((void**)&d2, blk2);
+        if (e == hipSuccess) {
+            A.out_text = (uint16_t*)d2;
+            A.out_spans = (ptx_span*)(d2 + ot_bytes);
+            A.out_span_unit = (uint32_t*)(d2 + ot_bytes + os_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            if (out_units) hipLaunchKernelGGL(ptx_slice_copy_kernel, dim3((uint32_t)((out_units + PTX_SLICE_BLOCK - 1) / PTX_SLICE_BLOCK)), dim3(64), 0, ctx->stream, A);
+            if (out_rows) hipLaunchKernelGGL(ptx_slice_span_kernel, dim3((uint32_t)((out_rows + 255) / 256)), dim3(256), 0, ctx->stream, A, out_rows);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess && out_units) e = hipMemcpyAsync(hp1, d2, out_units * 2, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out_rows) e = hipMemcpyAsync(hp1 + ot_bytes, d2 + ot_bytes, os_bytes + out_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
+    }
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    (void)ptx_dev_free(d2);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("text slices: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->n_slices = ns;
+    out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->status = (const uint32_t*)hp0;
+    out->elem_start = (const uint32_t*)(hp0 + es_at);
+    out->elem_end = (const uint32_t*)(hp0 + ee_at);
+    out->unit_off = out_off;
+    out->sspan_off = out_off + nso;
+    out->text = (const uint16_t*)hp1;
+    out->sspans = (const ptx_span*)(hp1 + ot_bytes);
+    out->sspan_unit = (const uint32_t*)(hp1 + ot_bytes + os_bytes);
     out->owner = h;
     return PTX_OK;
 }

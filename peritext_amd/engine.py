@@ -373,6 +373,41 @@ class Engine:
         finally:
             self.lib.ptx_matches_free(C.byref(m))
 
+    def text_slices(self, dbatch, dresult, dstrings, slices, first_log=0, n_logs=None):
+        """The text and the span rows of element ranges of the logs [first_log, first_log + n_logs), cut on the device without downloading the documents
+        (ptx_result_text_slices): wire.Slices.  `slices` holds, per log of the range, a list of (start, end) visible element indexes with
+        Array.prototype.slice's clamping for non-negative arguments (0xFFFFFFFF is a legal bound); a log's slices may come in any order, overlap and repeat,
+        and every output follows that order: hits of find_text widened by some context, a result's cintervals, a viewport."""
+        if n_logs is None:
+            n_logs = self.n_logs(dbatch) - first_log
+        if len(slices) != n_logs:
+            raise ValueError("slices holds %d lists for %d logs" % (len(slices), n_logs))
+        off = np.zeros(n_logs + 1, dtype=np.uint64)
+        if n_logs:
+            off[1:] = np.cumsum([len(s) for s in slices], dtype=np.uint64)
+        flat = np.array([p for s in slices for p in s], dtype=np.uint32).reshape(-1, 2)
+        start, end = np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
+        return self.text_slices_flat(dbatch, dresult, dstrings, off, start, end, first_log, n_logs)
+
+    def text_slices_flat(self, dbatch, dresult, dstrings, slice_off, slice_start, slice_end, first_log=0, n_logs=None):
+        """text_slices with the C ABI's own arrays: slice_off u64 [n_logs + 1], slice_start / slice_end u32 [slice_off[n_logs]] (numpy; None passes NULL)."""
+        if n_logs is None:
+            n_logs = self.n_logs(dbatch) - first_log
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None and len(a) else C.cast(None, t)  # noqa: E731
+        m = abi.ptx_slices()
+        self._check(self.lib.ptx_result_text_slices(self.ctx, dbatch, dresult, dstrings, first_log, n_logs, ptr(slice_off, abi.u64p), ptr(slice_start, abi.u32p),
+                                                    ptr(slice_end, abi.u32p), C.byref(m)))
+        try:
+            n, k, arr = int(m.n_logs), int(m.n_slices), _copied
+            unit_off, sspan_off = arr(m.unit_off, np.uint64, k + 1), arr(m.sspan_off, np.uint64, k + 1)
+            nr = int(sspan_off[k])
+            return wire.Slices(status=arr(m.status, np.uint32, n), slice_off=np.array(slice_off, dtype=np.uint64) if n else np.zeros(1, np.uint64),
+                               elem_start=arr(m.elem_start, np.uint32, k), elem_end=arr(m.elem_end, np.uint32, k), unit_off=unit_off,
+                               text=arr(m.text, np.uint16, int(unit_off[k])), sspan_off=sspan_off, sspans=arr(m.sspans, abi.SPAN_DTYPE, nr),
+                               sspan_unit=arr(m.sspan_unit, np.uint32, nr), kernel_ms=float(m.kernel_ms))
+        finally:
+            self.lib.ptx_slices_free(C.byref(m))
+
     def replay_patches(self, dbatch, dresult, first_row=None):
         """The Patch[] stream every applyChange of every log would have returned (reference/src/micromerge.ts:499),
         as wire.Patches; `dresult` = the merge of the same batch (engine created without FLAG_NO_ELEM_RANK).

@@ -92,6 +92,9 @@ struct Lib {
     /* find in that text without downloading it */
     ptx_status (*result_find_text)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, const uint16_t*, uint32_t, uint32_t, uint32_t, ptx_matches*) = nullptr;
     void (*matches_free)(ptx_matches*) = nullptr;
+    /* the text and span rows of element ranges */
+    ptx_status (*result_text_slices)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, const uint64_t*, const uint32_t*, const uint32_t*, ptx_slices*) = nullptr;
+    void (*slices_free)(ptx_slices*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -142,7 +145,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches") &&
                   sym(L.batch_at_versions, "ptx_batch_at_versions") && sym(L.strings_upload, "ptx_strings_upload") && sym(L.strings_free, "ptx_strings_free") &&
                   sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free") && sym(L.result_find_text, "ptx_result_find_text") &&
-                  sym(L.matches_free, "ptx_matches_free");
+                  sym(L.matches_free, "ptx_matches_free") && sym(L.result_text_slices, "ptx_result_text_slices") && sym(L.slices_free, "ptx_slices_free");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -668,6 +671,70 @@ napi_value FindText(napi_env env, napi_callback_info info) {
         if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
     }
     L.matches_free(&m);
+    return out;
+}
+
+/* ---- the text and span rows of element ranges (INTEGRATION.md "Snippets without downloading the text"): textSlices(ctx, batch, strings, sliceOff: BigUint64Array
+ *      [nLogs + 1], sliceStart, sliceEnd: Uint32Array) uploads, merges and cuts in one call (ptx_result_text_slices) -> the merge's compact rows (as
+ *      applyMaterialize: the comment intervals resolve a row's comment ids) + {sliceStatus: Uint32Array [nLogs], elemStart / elemEnd: Uint32Array [nSlices],
+ *      unitOff / sspanOff: BigUint64Array [nSlices + 1], sliceText: Uint16Array, sspans: Uint32Array (start, attr pairs), sspanUnit: Uint32Array, kernelMs} ---- */
+static bool typed_arg(napi_env env, napi_value v, napi_typedarray_type want, void** data, size_t* n) {
+    bool is = false;
+    napi_typedarray_type tp;
+    napi_value ab;
+    size_t offset = 0;
+    return napi_is_typedarray(env, v, &is) == napi_ok && is && napi_get_typedarray_info(env, v, &tp, n, data, &ab, &offset) == napi_ok && tp == want;
+}
+napi_value TextSlices(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 5 ? ctx_of(env, argv[0]) : nullptr;
+    ptx_dstrings* ds = ctx ? strings_of(env, argv[2]) : nullptr;
+    if (!ds) return throw_msg(env, "textSlices(ctx, batch, strings, sliceOff: BigUint64Array, sliceStart: Uint32Array, sliceEnd: Uint32Array)");
+    void *off = nullptr, *start = nullptr, *end = nullptr;
+    size_t n_off = 0, n_start = 0, n_end = 0;
+    if (!typed_arg(env, argv[3], napi_biguint64_array, &off, &n_off) || !typed_arg(env, argv[4], napi_uint32_array, &start, &n_start) || !typed_arg(env, argv[5], napi_uint32_array, &end, &n_end))
+        return throw_msg(env, "textSlices: sliceOff must be a BigUint64Array, sliceStart and sliceEnd Uint32Arrays");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    if (n_off != (size_t)pb.n_logs + 1 || n_start != n_end || ((const uint64_t*)off)[pb.n_logs] != n_start)
+        return throw_msg(env, "textSlices: sliceOff holds nLogs + 1 offsets, the last one the length of sliceStart and sliceEnd");
+    ptx_dbatch* db = nullptr;
+    ptx_dresult* dr = nullptr;
+    ptx_result res;
+    ptx_slices m;
+    bool have_res = false;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.result_alloc(ctx, db, &dr);
+    if (st == PTX_OK) st = L.merge(ctx, db, dr);
+    if (st == PTX_OK) st = L.result_download(ctx, db, dr, &res);
+    have_res = st == PTX_OK;
+    if (st == PTX_OK) st = L.result_text_slices(ctx, db, dr, ds, 0, pb.n_logs, (const uint64_t*)off, n_start ? (const uint32_t*)start : nullptr, n_start ? (const uint32_t*)end : nullptr, &m);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (dr) L.dresult_free(ctx, dr);
+    if (db) L.batch_free(ctx, db);
+    if (st != PTX_OK) {
+        if (have_res) L.result_free(&res);
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "textSlices (ptx_merge / ptx_result_text_slices) failed (status %d): %s", st, err.c_str());
+        return throw_msg(env, msg);
+    }
+    napi_value out = result_to_js(env, res, nullptr), v;
+    if (out) {
+        const size_t nl = (size_t)m.n_logs, ns = (size_t)m.n_slices, nu = (size_t)m.unit_off[ns], nr = (size_t)m.sspan_off[ns];
+        if ((v = make_u32(env, m.status, nl))) napi_set_named_property(env, out, "sliceStatus", v);
+        if ((v = make_u32(env, m.elem_start, ns))) napi_set_named_property(env, out, "elemStart", v);
+        if ((v = make_u32(env, m.elem_end, ns))) napi_set_named_property(env, out, "elemEnd", v);
+        if ((v = make_typed(env, napi_biguint64_array, 8, m.unit_off, ns + 1))) napi_set_named_property(env, out, "unitOff", v);
+        if ((v = make_typed(env, napi_biguint64_array, 8, m.sspan_off, ns + 1))) napi_set_named_property(env, out, "sspanOff", v);
+        if ((v = make_typed(env, napi_uint16_array, 2, m.text, nu))) napi_set_named_property(env, out, "sliceText", v);
+        if ((v = make_u32(env, m.sspans, 2 * nr))) napi_set_named_property(env, out, "sspans", v);
+        if ((v = make_u32(env, m.sspan_unit, nr))) napi_set_named_property(env, out, "sspanUnit", v);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.slices_free(&m);
     return out;
 }
 
@@ -1283,7 +1350,8 @@ napi_value Init(napi_env env, napi_value exports) {
                                               {"stringsUpload", nullptr, StringsUpload, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"stringsFree", nullptr, StringsFree, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"resultText", nullptr, ResultText, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"findText", nullptr, FindText, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"findText", nullptr, FindText, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"textSlices", nullptr, TextSlices, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

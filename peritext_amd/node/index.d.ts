@@ -124,6 +124,10 @@ export class MergeEngine {
     /** every position of `needle` in every replica's text, found on the device without downloading the text (ptx_result_find_text): indexOf repeated from p + 1 over UTF-16
      *  code units; count = all matches, hits = the first opts.maxHits (default: all), ascending; [startIndex, endIndex) is the visible element range change() takes */
     findText(docs: Change[][][], needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number }): Array<Array<{ status: number; count: number; hits: Array<{ unit: number; startIndex: number; endIndex: number }> }>>
+    /** the text, with its formatting, of element ranges of every replica, cut on the device without downloading the documents' text (ptx_result_text_slices):
+     *  Array.prototype.slice's clamping for non-negative indexes; a replica's ranges may come in any order, overlap and repeat; per range, in that order, the range
+     *  after clamping and the FormatSpanWithText[] of its elements */
+    textSlices(docs: Change[][][], ranges: Array<Array<Array<{ startIndex: number; endIndex: number }>>>, opts?: {}): Array<Array<Array<{ status: number; startIndex: number; endIndex: number; spans: FormatSpanWithText[] }>>>
     /** spans as applyChanges + patches[doc][replica][change] = what applyChange(change) returns (micromerge.ts:499) */
     applyChangesWithPatches(docs: Change[][][]): { spans: FormatSpanWithText[][][]; patches: Patch[][][][] }
     /** patch streams (patchOff / patchLogs / patches of `res`: this library's, or a peer's) back into the documents they describe (ptx_accumulate_patches) */

@@ -912,6 +912,50 @@ class MergeEngine {
             return { status: m.status[l], count: m.nMatches[l], hits }
         }))
     }
+    /** The text, with its formatting, of element ranges of every replica, cut on the device without downloading the documents' text (ptx_result_text_slices):
+     *  encode, upload, merge and cut in one call.  ranges[doc][replica] = Array<{ startIndex, endIndex }> of visible element indexes with
+     *  Array.prototype.slice's clamping for non-negative arguments (hits of findText widened by some context, comment intervals, a viewport); a replica's
+     *  ranges may come in any order, overlap and repeat.  Per range, in that order, { status, startIndex, endIndex, spans }: the range after clamping and the
+     *  FormatSpanWithText[] of its elements — what cutting getTextWithFormatting's result down to them gives.  A replica whose merge failed has its status
+     *  and empty ranges. */
+    textSlices(docs, ranges, opts) {
+        const batch = encodeDocs(docs)
+        const nLogs = batch.logOff.length - 1
+        const off = new BigUint64Array(nLogs + 1)
+        const flat = []
+        let log = 0
+        if (!Array.isArray(ranges) || ranges.length !== docs.length) throw new RangeError("ranges: one entry per document")
+        docs.forEach((logs, d) => {
+            if (!Array.isArray(ranges[d]) || ranges[d].length !== logs.length) throw new RangeError("ranges[" + d + "]: one entry per replica")
+            logs.forEach((_, r) => {
+                for (const x of ranges[d][r]) {
+                    if (!Number.isInteger(x.startIndex) || !Number.isInteger(x.endIndex) || x.startIndex < 0 || x.endIndex < 0 || x.startIndex > 0xFFFFFFFF || x.endIndex > 0xFFFFFFFF)
+                        throw new RangeError("ranges: startIndex and endIndex are unsigned 32-bit integers")
+                    flat.push(x)
+                }
+                off[++log] = BigInt(flat.length)
+            })
+        })
+        const start = Uint32Array.from(flat, x => x.startIndex), end = Uint32Array.from(flat, x => x.endIndex)
+        const m = this._withStrings(batch, strings => this.addon.textSlices(this.ctx, batch, strings, off, start, end))
+        log = 0
+        return docs.map(logs => logs.map(() => {
+            const l = log++, out = []
+            const st = m.logs[12 * l] || m.sliceStatus[l]
+            const bc = Number(m.cintOff[l]), nCints = m.logs[12 * l + 5], comments = batch.docComments[batch.logDoc[l]]
+            for (let k = Number(off[l]); k < Number(off[l + 1]); k++) {
+                const u0 = Number(m.unitOff[k]), u1 = Number(m.unitOff[k + 1]), r0 = Number(m.sspanOff[k]), r1 = Number(m.sspanOff[k + 1])
+                const whole = Buffer.from(m.sliceText.buffer, m.sliceText.byteOffset + 2 * u0, 2 * (u1 - u0)).toString("utf16le")
+                const spans = []
+                for (let q = r0; q < r1; q++) {
+                    const text = whole.slice(m.sspanUnit[q], q + 1 < r1 ? m.sspanUnit[q + 1] : u1 - u0)
+                    spans.push({ text, marks: spanMarks(batch, m, m.sspans[2 * q + 1], m.sspans[2 * q], bc, nCints, comments) })
+                }
+                out.push({ status: st, startIndex: m.elemStart[k], endIndex: m.elemEnd[k], spans })
+            }
+            return out
+        }))
+    }
     /** Per-document digests (2 x u64 as BigInt pairs) of every log: equal digests <=> deep-equal spans. */
     digests(docs) {
         const batch = encodeDocs(docs)

@@ -838,6 +838,59 @@ def decode_spans_text(batch, res, text, log):
     return out
 
 
+@dataclass
+class Slices:
+    """Host view of ptx_slices (Engine.text_slices): log l of the range has the slices slice_off[l] .. slice_off[l + 1], in the caller's order.  Slice k covers
+    the visible elements [elem_start[k], elem_end[k]) after clamping, its code units are text[unit_off[k] : unit_off[k + 1]], its span rows the rows
+    sspan_off[k] .. sspan_off[k + 1] of sspans (start: a DOCUMENT element index, attr) and sspan_unit (the code-unit offset of that start within the slice)."""
+
+    status: np.ndarray  # u32 [n_logs] exactly Text.status of the same range
+    slice_off: np.ndarray  # u64 [n_logs + 1] the caller's
+    elem_start: np.ndarray  # u32 [n_slices]
+    elem_end: np.ndarray  # u32 [n_slices]
+    unit_off: np.ndarray  # u64 [n_slices + 1]
+    text: np.ndarray  # u16 [unit_off[n_slices]]
+    sspan_off: np.ndarray  # u64 [n_slices + 1]
+    sspans: np.ndarray  # SPAN_DTYPE [sspan_off[n_slices]]
+    sspan_unit: np.ndarray  # u32 ...
+    kernel_ms: float = 0.0
+
+    def index(self, log, j):
+        """The number of slice j of log `log` in the flat arrays."""
+        k = int(self.slice_off[log]) + j
+        if not (0 <= j and k < int(self.slice_off[log + 1])):
+            raise IndexError("log %d has no slice %d" % (log, j))
+        return k
+
+    def of_slice(self, k):
+        """The text of slice k as a str (JS string semantics: lone surrogates stay)."""
+        return self.text[int(self.unit_off[k]) : int(self.unit_off[k + 1])].astype("<u2").tobytes().decode("utf-16-le", "surrogatepass")
+
+    def rows_of_slice(self, k):
+        """[(start, attr, unit)] of slice k's span rows."""
+        a, b = int(self.sspan_off[k]), int(self.sspan_off[k + 1])
+        return [(int(self.sspans[r]["start"]), int(self.sspans[r]["attr"]), int(self.sspan_unit[r])) for r in range(a, b)]
+
+
+def decode_slice_spans(batch, res, slices, log, j):
+    """FormatSpanWithText[] of slice j of log `log`: what cutting decode_spans_text's result down to the slice's elements gives — every row's text ONE slice of
+    the slice's text, comment ids resolved against `res`'s cintervals at the row's (document) start.  `res` and `slices` cover the same range of logs."""
+    st = int(res.logs[log]["status"]) or int(slices.status[log])
+    if st != 0:
+        raise ValueError(abi.STATUS_NAMES.get(st, "error %d" % st))
+    k = slices.index(log, j)
+    _, _, c = canonical_of_log(batch, res, log)
+    comments = batch.doc_comments[batch.log_doc[log]]
+    units = slices.text[int(slices.unit_off[k]) : int(slices.unit_off[k + 1])].astype("<u2")
+    rows = slices.rows_of_slice(k)
+    cut = [u for _, _, u in rows] + [len(units)]
+    out = []
+    for q, (start, attr, _) in enumerate(rows):
+        ids = [int(ci["id"]) for ci in c if int(ci["start"]) <= start < int(ci["end"])] if attr & abi.ATTR_COMMENT else []
+        out.append({"text": units[cut[q] : cut[q + 1]].tobytes().decode("utf-16-le", "surrogatepass"), "marks": _marks_of_attr(batch, attr, ids, comments)})
+    return out
+
+
 def decode_patches(batch, pat, log, with_rows=False):
     """Patch[] of one log in application order, in the reference's shapes (reference/src/micromerge.ts:214-222 Patch,
     :661-671 insert, :696-703 delete, src/peritext.ts:251-281 add/removeMark).  The makeList patch (the op itself,
