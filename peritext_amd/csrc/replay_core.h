@@ -218,6 +218,9 @@ template <uint32_t kThreads>
 PTX_DEV void ptx_replay_reserve(const PtxReplayArgs& A, PtxReplayHdr* H, uint32_t t0, uint32_t first, uint32_t N, uint32_t npatch, uint32_t& room, uint32_t& ext_left) {
     uint32_t rate = 3u * (npatch / (t0 > first ? t0 - first + 1u : 1u) + 1u);
     rate = rate < 8u ? 8u : rate;
+    /* a chunk that beat the room has lost records: an extent granted now would make room for the count, not for them, and the log would report PTX_OK over a
+     * stream with a hole.  It takes no extent any more, so it ends with produced > room: PTX_ERR_CAPACITY */
+    if (t0 > first && npatch > room) ext_left = 0u;
     if (ext_left && t0 + PTX_RCHUNK > first && npatch + rate * PTX_RCHUNK > room) {
         rate *= ext_left == 2u ? 1u : 16u;
         const uint64_t want64 = (uint64_t)rate * (N - t0) + 1024u;
