@@ -757,6 +757,70 @@ ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_d
                                   const uint64_t* slice_off, const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out);
 void ptx_slices_free(ptx_slices* m);
 
+/* ---- a resident text view: search and snippets without re-assembling the text ----
+ * ptx_result_find_text and ptx_result_text_slices assemble the documents' text per call, and a slice call rebuilds the element prefix as well.  A view holds
+ * both for the logs [first_log, first_log + n_logs) of ONE merge; it is made once and queried any number of times.  It owns, in device memory of its own (not the
+ * context's pool of small blocks), what ptx_result_text_range returns for the range — status, text_off, span_off, text, span_unit — and, for every log that is
+ * PTX_OK, the exclusive element prefix pre[0 .. n_visible] (pre[e] = the code-unit offset of visible element e in the log's text) with its offsets, and the
+ * batch's row offsets of the range.
+ *   cost               2 bytes per code unit + 4 per span row + 4 per visible element (+ 4 per good log) + 52 per log.  The 49 152 `rich4k` logs of DESIGN §3k:
+ *                      184 MB of text + 367 MB of prefix
+ *   lifetimes          once ptx_text_view_create has returned the view reads nothing of `b` or `s`: `s` may be freed.  It reads the span rows of `r` — and
+ *                      nothing else of it: a log's n_visible is taken from the view's own prefix — in slice and snippet calls: `r` must outlive the view
+ *                      and stay the merge it was made from (a ptx_merge into `r` after an append makes the view stale: free it and make a new one)
+ *   ptx_view_find_text / ptx_view_text_slices   every field of ptx_matches / ptx_slices equals what ptx_result_find_text / ptx_result_text_slices return for the
+ *                      same (b, r, s, range) — kernel_ms excepted —, the argument errors are the same, plus PTX_ERR_INVALID_ARG for a NULL view.  No text pass
+ *                      and no prefix pass runs
+ *   ptx_view_find_snippets   find, then ONE snippet per listed hit, in hit order, without the hits leaving the device in between: n_slices == hit_off[n_logs],
+ *                      slice k belongs to hit k.  The snippet of hit k is the slice [hit_start[k] - before, hit_end[k] + after) — the subtraction saturates at
+ *                      0, the addition at 0xFFFFFFFF; `before` and `after` may be 0 or 0xFFFFFFFF — clamped exactly as ptx_result_text_slices clamps.
+ *                      match_unit[k] = hit_unit[k] - pre[elem_start[k]] is the code-unit offset of the match within snippet k's text:
+ *                      text[unit_off[k] + match_unit[k] .. + n_pattern) is the pattern (after folding under PTX_FIND_ASCII_NOCASE).  It cannot be derived
+ *                      from element counts: an element may hold many units.  Overlapping hits give overlapping snippets, nothing is merged.
+ *                      max_hits_per_log == 0 is the count-only answer with zero snippets
+ * A range outside the batch is PTX_ERR_INVALID_ARG.  n_logs == 0 makes a legal empty view; every query on it returns the empty result of its ptx_result_* twin.
+ * elem_rank is not needed (PTX_FLAG_NO_ELEM_RANK contexts work).  ptx_text_view_create and every query synchronise. */
+typedef struct ptx_dview ptx_dview;
+typedef struct ptx_view_desc {
+    uint32_t n_logs;
+    uint32_t first_log;
+    uint64_t n_units;              /* code units of the range: text_off[n_logs] */
+    uint64_t n_prefix_words;       /* words of the element prefix: the sum of n_visible + 1 over the logs that are PTX_OK */
+    uint64_t bytes;                /* device memory the view holds */
+    float kernel_ms;               /* HIP events around every launch of ptx_text_view_create */
+    uint32_t reserved;
+} ptx_view_desc;
+typedef struct ptx_snippets {
+    uint32_t n_logs;
+    uint32_t n_pattern;
+    float kernel_ms;               /* HIP events around every launch of the call */
+    uint32_t n_slices;             /* == hit_off[n_logs] */
+    const uint32_t* status;        /* [n_logs] as ptx_matches */
+    const uint32_t* n_matches;     /* [n_logs] */
+    const uint64_t* hit_off;       /* [n_logs + 1] */
+    const uint32_t* hit_unit;      /* [n_slices] */
+    const uint32_t* hit_start;
+    const uint32_t* hit_end;
+    const uint32_t* elem_start;    /* [n_slices] as ptx_slices, of the slice [hit_start - before, hit_end + after) */
+    const uint32_t* elem_end;
+    const uint64_t* unit_off;      /* [n_slices + 1] */
+    const uint16_t* text;          /* [unit_off[n_slices]] */
+    const uint64_t* sspan_off;     /* [n_slices + 1] */
+    const ptx_span* sspans;        /* [sspan_off[n_slices]] */
+    const uint32_t* sspan_unit;
+    const uint32_t* match_unit;    /* [n_slices] code-unit offset of the match within the snippet's text */
+    void* owner;
+} ptx_snippets;
+ptx_status ptx_text_view_create(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, ptx_dview** out);
+void ptx_text_view_free(ptx_ctx* ctx, ptx_dview* v);
+ptx_status ptx_view_info(ptx_ctx* ctx, const ptx_dview* v, ptx_view_desc* out);
+/* Owned by the library until ptx_matches_free / ptx_slices_free / ptx_snippets_free. */
+ptx_status ptx_view_find_text(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, ptx_matches* out);
+ptx_status ptx_view_text_slices(ptx_ctx* ctx, const ptx_dview* v, const uint64_t* slice_off, const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out);
+ptx_status ptx_view_find_snippets(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log,
+                                  uint32_t before, uint32_t after, ptx_snippets* out);
+void ptx_snippets_free(ptx_snippets* m);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

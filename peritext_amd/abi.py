@@ -323,6 +323,43 @@ class ptx_slices(C.Structure):
     ]
 
 
+# a resident text view (ptx_text_view_create and the ptx_view_* queries; peritext_amd/csrc/view_core.h)
+class ptx_view_desc(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("first_log", C.c_uint32),
+        ("n_units", C.c_uint64),
+        ("n_prefix_words", C.c_uint64),
+        ("bytes", C.c_uint64),
+        ("kernel_ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class ptx_snippets(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("n_pattern", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("n_slices", C.c_uint32),
+        ("status", u32p),
+        ("n_matches", u32p),
+        ("hit_off", u64p),
+        ("hit_unit", u32p),
+        ("hit_start", u32p),
+        ("hit_end", u32p),
+        ("elem_start", u32p),
+        ("elem_end", u32p),
+        ("unit_off", u64p),
+        ("text", u16p),
+        ("sspan_off", u64p),
+        ("sspans", C.c_void_p),
+        ("sspan_unit", u32p),
+        ("match_unit", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
 # numpy dtypes with the same layout
 import numpy as np  # noqa: E402
 
@@ -418,6 +455,13 @@ FUNCTIONS = {
     "ptx_matches_free": (None, [C.POINTER(ptx_matches)]),
     "ptx_result_text_slices": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, u64p, u32p, u32p, C.POINTER(ptx_slices)]),
     "ptx_slices_free": (None, [C.POINTER(ptx_slices)]),
+    "ptx_text_view_create": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "ptx_text_view_free": (None, [vp, vp]),
+    "ptx_view_info": (C.c_int32, [vp, vp, C.POINTER(ptx_view_desc)]),
+    "ptx_view_find_text": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_matches)]),
+    "ptx_view_text_slices": (C.c_int32, [vp, vp, u64p, u32p, u32p, C.POINTER(ptx_slices)]),
+    "ptx_view_find_snippets": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_snippets)]),
+    "ptx_snippets_free": (None, [C.POINTER(ptx_snippets)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

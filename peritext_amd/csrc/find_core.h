@@ -118,16 +118,25 @@ PTX_DEV uint32_t ptx_find_holder(const uint32_t* pre, uint32_t nt, uint32_t u) {
     return lo;
 }
 
+/* The position half of the emit pass, callable alone (view_core.h maps the hits to elements by a search over a resident prefix instead of the tile walk below):
+ * hit_unit of the log's listed hits — the first hit_off[l + 1] - hit_off[l] of them.  Returns their number: 0 for a log without text, without a match, or in a
+ * count-only call.  Reads nothing of T but status, off and text. */
+template <uint32_t kThreads>
+PTX_DEV uint32_t ptx_find_positions_log(const PtxFindArgs& A, uint32_t l, uint8_t* lds) {
+    const uint32_t nh = (uint32_t)(A.hit_off[l + 1u] - A.hit_off[l]);
+    if (nh != 0u) (void)ptx_find_walk<kThreads, true>(A, l, lds, nh, A.hit_unit + A.hit_off[l]);
+    return nh;
+}
+
 template <uint32_t kThreads>
 PTX_DEV void ptx_find_emit_log(const PtxFindArgs& A, uint32_t l, uint8_t* lds) {
     PtxFindHdr* H = (PtxFindHdr*)lds;
     uint32_t* pre = (uint32_t*)(lds + PTX_FIND_LDS_PRE);
-    const uint32_t nh = (uint32_t)(A.hit_off[l + 1u] - A.hit_off[l]);
-    if (nh == 0u) return; /* a log without text, without a match, or a count-only call */
-    uint32_t* hu = A.hit_unit + A.hit_off[l];
+    const uint32_t nh = ptx_find_positions_log<kThreads>(A, l, lds);
+    if (nh == 0u) return;
+    const uint32_t* hu = A.hit_unit + A.hit_off[l];
     uint32_t* hs = A.hit_start + A.hit_off[l];
     uint32_t* he = A.hit_end + A.hit_off[l];
-    (void)ptx_find_walk<kThreads, true>(A, l, lds, nh, hu);
     PTX_SYNC_FULL(); /* a lane's hit_unit stores are read by other lanes below */
     const uint32_t log = A.T.first_log + l;
     const uint32_t nv = ptx_text_rows(A.T, log, A.T.logs[log].n_visible);

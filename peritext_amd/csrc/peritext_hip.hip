@@ -40,6 +40,7 @@
 #include "text_core.h"
 #include "find_core.h"
 #include "slice_core.h"
+#include "view_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -659,6 +660,26 @@ extern "C" __global__ void __launch_bounds__(64) ptx_slice_copy_kernel(PtxSliceA
 extern "C" __global__ void __launch_bounds__(256) ptx_slice_span_kernel(PtxSliceArgs A, uint64_t n_rows) {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r < n_rows) ptx_slice_span_one(A, r);
+}
+
+/* ---- a resident text view (view_core.h): a lane per log plans the prefix of EVERY good log (then ptx_slice_prefix_kernel writes it); per query one wave per log
+ *      lists its first hits' positions (find_core.h's position half), a lane per listed hit finds its elements in the resident prefix, and for snippets a lane
+ *      per hit writes the window and match_unit; the slice kernels above do the rest ---- */
+extern "C" __global__ void __launch_bounds__(256) ptx_view_plan_kernel(PtxSliceArgs A, uint64_t* every_log) {
+    const uint32_t l = blockIdx.x * 256u + threadIdx.x;
+    if (l < A.T.n_logs) ptx_view_plan_one(A, every_log, l);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_view_positions_kernel(PtxFindArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_find_lds[PTX_FIND_LDS_PRE]; /* the header, the pattern and the step's units: no tile scan */
+    if (blockIdx.x < A.T.n_logs) (void)ptx_find_positions_log<64>(A, blockIdx.x, ptx_find_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_view_locate_kernel(PtxViewArgs A) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < A.n_hits) ptx_view_locate_one(A, k); /* (the grid is ceil(n_hits / 256) <= 2^24 blocks: k does not wrap) */
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_view_windows_kernel(PtxViewArgs A) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < A.n_hits) ptx_view_windows_one(A, k);
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -2462,6 +2483,40 @@ void ptx_slices_free(ptx_slices* m) {
     memset(m, 0, sizeof(*m));
 }
 
+/* the copy and span passes of ptx_result_text_slices, ptx_view_text_slices and ptx_view_find_snippets over bounds that are on the device, and their download: a block,
+ * device and pinned host alike, of text | sspans | sspan_unit.  The pinned block becomes h->pinned[slot]; the device block goes back to the pool before this returns */
+static hipError_t slice_emit_passes(ptx_ctx* ctx, PtxSliceArgs& A, uint64_t out_units, uint64_t out_rows, ptx_host_result* h, int slot, uint64_t* ot_bytes, uint64_t* os_bytes, float* ms) {
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    *ot_bytes = a16(out_units * 2);
+    *os_bytes = a16(out_rows * sizeof(ptx_span));
+    const uint64_t blk = *ot_bytes + *os_bytes + a16(out_rows * 4) + 16;
+    uint8_t *hp = nullptr, *d = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp, blk, hipHostMallocDefault);
+    h->pinned[slot] = hp;
+    if (e == hipSuccess && (out_units || out_rows)) {
+        e = ptx_dev_malloc((void**)&d, blk);
+        if (e == hipSuccess) {
+            A.out_text = (uint16_t*)d;
+            A.out_spans = (ptx_span*)(d + *ot_bytes);
+            A.out_span_unit = (uint32_t*)(d + *ot_bytes + *os_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            if (out_units) hipLaunchKernelGGL(ptx_slice_copy_kernel, dim3((uint32_t)((out_units + PTX_SLICE_BLOCK - 1) / PTX_SLICE_BLOCK)), dim3(64), 0, ctx->stream, A);
+            if (out_rows) hipLaunchKernelGGL(ptx_slice_span_kernel, dim3((uint32_t)((out_rows + 255) / 256)), dim3(256), 0, ctx->stream, A, out_rows);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess && out_units) e = hipMemcpyAsync(hp, d, out_units * 2, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out_rows) e = hipMemcpyAsync(hp + *ot_bytes, d + *ot_bytes, *os_bytes + out_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(ms, ctx->ev0, ctx->ev1);
+        (void)ptx_dev_free(d);
+    }
+    return e;
+}
+
 ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, const uint64_t* slice_off,
                                   const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out) {
     if (!ctx || !b || !r || !s || !out) return PTX_ERR_INVALID_ARG;
@@ -2486,7 +2541,7 @@ ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_d
     const uint64_t so_at = down0, ss_at = so_at + a16(no * 8), se_at = ss_at + col, up_end = se_at + col;
     const uint64_t hblk0 = up_end + 32;
     const uint64_t off_at = up_end, po_at = off_at + a16(2 * no * 8), sl_at = po_at + a16(2 * no * 8), fs_at = sl_at + col, src_at = fs_at + col, dblk0 = src_at + a16(ns64 * 8);
-    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr;
     hipError_t e = hipHostMalloc((void**)&hp0, hblk0, hipHostMallocDefault);
     h->pinned[0] = hp0;
     if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, dblk0);
@@ -2582,32 +2637,11 @@ ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_d
         }
     }
     /* block 2, device and pinned host alike: text | sspans | sspan_unit */
-    const uint64_t ot_bytes = a16(out_units * 2), os_bytes = a16(out_rows * sizeof(ptx_span)), blk2 = ot_bytes + os_bytes + a16(out_rows * 4) + 16;
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
-    h->pinned[1] = hp1;
-    if (e == hipSuccess && (out_units || out_rows)) {
-        e = ptx_dev_malloc((void**)&d2, blk2);
-        if (e == hipSuccess) {
-            A.out_text = (uint16_t*)d2;
-            A.out_spans = (ptx_span*)(d2 + ot_bytes);
-            A.out_span_unit = (uint32_t*)(d2 + ot_bytes + os_bytes);
-            e = hipEventRecord(ctx->ev0, ctx->stream);
-        }
-        if (e == hipSuccess) {
-            if (out_units) hipLaunchKernelGGL(ptx_slice_copy_kernel, dim3((uint32_t)((out_units + PTX_SLICE_BLOCK - 1) / PTX_SLICE_BLOCK)), dim3(64), 0, ctx->stream, A);
-            if (out_rows) hipLaunchKernelGGL(ptx_slice_span_kernel, dim3((uint32_t)((out_rows + 255) / 256)), dim3(256), 0, ctx->stream, A, out_rows);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess && out_units) e = hipMemcpyAsync(hp1, d2, out_units * 2, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && out_rows) e = hipMemcpyAsync(hp1 + ot_bytes, d2 + ot_bytes, os_bytes + out_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        else (void)hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
-    }
+    uint64_t ot_bytes = 0, os_bytes = 0;
+    if (e == hipSuccess) e = slice_emit_passes(ctx, A, out_units, out_rows, h, 1, &ot_bytes, &os_bytes, &ms[2]);
+    hp1 = (uint8_t*)h->pinned[1];
     (void)ptx_dev_free(d0);
     (void)ptx_dev_free(d1);
-    (void)ptx_dev_free(d2);
     if (e != hipSuccess) {
         delete h;
         return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("text slices: ") + hipGetErrorString(e));
@@ -2615,6 +2649,441 @@ ptx_status ptx_result_text_slices(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_d
     out->n_logs = n_logs;
     out->n_slices = ns;
     out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->status = (const uint32_t*)hp0;
+    out->elem_start = (const uint32_t*)(hp0 + es_at);
+    out->elem_end = (const uint32_t*)(hp0 + ee_at);
+    out->unit_off = out_off;
+    out->sspan_off = out_off + nso;
+    out->text = (const uint16_t*)hp1;
+    out->sspans = (const ptx_span*)(hp1 + ot_bytes);
+    out->sspan_unit = (const uint32_t*)(hp1 + ot_bytes + os_bytes);
+    out->owner = h;
+    return PTX_OK;
+}
+
+/* ---- a resident text view (view_core.h): the text passes and the element prefix of EVERY good log once, into blocks the view owns (plain hipMalloc: they are
+ *      large and live long, the pool of small blocks is for a call's scratch); then queries that run the find and slice passes over them.  Creation has two
+ *      waits: the sizes, the blocks.  A find has two (the number of listed hits, the hits), a slice call two (the sizes of the output, the output), a snippet
+ *      call three: what it saves over find + slices is every text and prefix pass, and the hits' trip to the host and back ---- */
+struct ptx_dview {
+    const ptx_dresult* r = nullptr; /* its span rows are read by slice and snippet calls */
+    uint32_t first_log = 0, n_logs = 0;
+    uint64_t n_units = 0, n_spans = 0, n_pre = 0, bytes = 0;
+    float kernel_ms = 0.f;
+    uint8_t *d0 = nullptr, *d1 = nullptr; /* d0: status | text_off, span_off | pre_off (two rows) | log_off | the plan's slice_off;  d1: text | span_unit | pre */
+    uint32_t* status = nullptr;
+    uint64_t *off = nullptr, *pre_off = nullptr, *log_off = nullptr;
+    uint16_t* text = nullptr;
+    uint32_t *span_unit = nullptr, *pre = nullptr;
+    std::vector<uint32_t> h_status; /* every query's result starts with it */
+};
+
+/* the text passes' arguments as a query sees them: the range is rebased to log 0 of the view's own log_off; no per-log rows, no values, no string table */
+static void view_text_args(const ptx_dview* v, PtxTextArgs& T) {
+    memset(&T, 0, sizeof(T));
+    T.log_off = v->log_off;
+    T.logs = nullptr; /* ptx_slice_visible then takes n_visible from the view's own prefix: the view and the bounds pass cannot disagree */
+    T.spans = v->r ? v->r->spans : nullptr;
+    T.first_log = 0;
+    T.n_logs = v->n_logs;
+    T.status = v->status;
+    T.off = v->off;
+    T.text = v->text;
+    T.span_unit = v->span_unit;
+}
+
+void ptx_text_view_free(ptx_ctx* ctx, ptx_dview* v) {
+    if (!v) return;
+    if (ctx) (void)ptx_enter(ctx);
+    (void)hipFree(v->d0);
+    (void)hipFree(v->d1);
+    delete v;
+}
+
+ptx_status ptx_text_view_create(ptx_ctx* ctx, const ptx_dbatch* b, const ptx_dresult* r, const ptx_dstrings* s, uint32_t first_log, uint32_t n_logs, ptx_dview** out) {
+    if (!ctx || !b || !r || !s || !out) return PTX_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (r->n_logs != b->n_logs || r->n_rows != b->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "result buffers do not match the batch");
+    if ((uint64_t)first_log + n_logs > r->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "log range exceeds the result");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_dview* v = new ptx_dview();
+    v->r = r;
+    v->first_log = first_log;
+    v->n_logs = n_logs;
+    v->h_status.resize(n_logs);
+    if (n_logs == 0) { /* the empty view holds nothing */
+        *out = v;
+        return PTX_OK;
+    }
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), off_at = st_bytes, po_at = off_at + a16(2 * no * 8), lo_at = po_at + a16(2 * no * 8), so_at = lo_at + a16(no * 8),
+                   blk0 = so_at + a16(no * 8);
+    float ms[2] = {0.f, 0.f};
+    uint64_t totals[3] = {0, 0, 0}; /* code units, spans, words of the prefix */
+    PtxSliceArgs A;
+    memset(&A, 0, sizeof(A));
+    hipError_t e = hipMalloc((void**)&v->d0, blk0);
+    if (e == hipSuccess) {
+        v->status = (uint32_t*)v->d0;
+        v->off = (uint64_t*)(v->d0 + off_at);
+        v->pre_off = (uint64_t*)(v->d0 + po_at);
+        v->log_off = (uint64_t*)(v->d0 + lo_at);
+        A.T.log_off = b->log_off;
+        A.T.logs = r->logs;
+        A.T.values = r->values;
+        A.T.spans = r->spans;
+        A.T.units = s->units;
+        A.T.str_off = s->off;
+        A.T.n_strings = s->n;
+        A.T.first_log = first_log;
+        A.T.n_logs = n_logs;
+        A.T.status = v->status;
+        A.T.off = v->off;
+        A.slice_off = (const uint64_t*)(v->d0 + so_at);
+        A.n_slices = n_logs;
+        A.pre_off = v->pre_off;
+        e = hipMemcpyAsync(v->log_off, b->log_off + first_log, no * 8, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ptx_text_length_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+        hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.T.off, n_logs);
+        hipLaunchKernelGGL(ptx_view_plan_kernel, dim3((n_logs + 255u) / 256u), dim3(256), 0, ctx->stream, A, (uint64_t*)(v->d0 + so_at));
+        hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.pre_off, n_logs);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->h_status.data(), v->status, (size_t)n_logs * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&totals[0], A.T.off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&totals[1], A.T.off + no + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&totals[2], A.pre_off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    else (void)hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+    if (e == hipSuccess && (totals[1] > r->n_rows || totals[2] > r->n_rows + n_logs)) e = hipErrorInvalidValue; /* (a log never produces more rows than it has ops) */
+    const uint64_t tx_bytes = a16(totals[0] * 2), su_bytes = a16(totals[1] * 4), blk1 = tx_bytes + su_bytes + a16(totals[2] * 4) + 16;
+    if (e == hipSuccess) e = hipMalloc((void**)&v->d1, blk1);
+    if (e == hipSuccess) {
+        A.T.text = v->text = (uint16_t*)v->d1;
+        A.T.span_unit = v->span_unit = (uint32_t*)(v->d1 + tx_bytes);
+        A.pre = v->pre = (uint32_t*)(v->d1 + tx_bytes + su_bytes);
+        e = hipEventRecord(ctx->ev0, ctx->stream);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ptx_text_assemble_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A.T);
+        hipLaunchKernelGGL(ptx_slice_prefix_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* the batch and the strings are free to go once this returns */
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+    }
+    if (e != hipSuccess) {
+        ptx_text_view_free(ctx, v);
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("text view: ") + hipGetErrorString(e));
+    }
+    v->n_units = totals[0];
+    v->n_spans = totals[1];
+    v->n_pre = totals[2];
+    v->bytes = blk0 + blk1;
+    v->kernel_ms = ms[0] + ms[1];
+    *out = v;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_info(ptx_ctx* ctx, const ptx_dview* v, ptx_view_desc* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->n_logs = v->n_logs;
+    out->first_log = v->first_log;
+    out->n_units = v->n_units;
+    out->n_prefix_words = v->n_pre;
+    out->bytes = v->bytes;
+    out->kernel_ms = v->kernel_ms;
+    return PTX_OK;
+}
+
+/* what a ptx_snippets owns: the find's two pinned blocks and the snippets' one */
+struct ptx_host_snippets {
+    ptx_host_result find, cut;
+};
+
+void ptx_snippets_free(ptx_snippets* m) {
+    if (!m) return;
+    delete (ptx_host_snippets*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+/* ptx_view_find_text (snip == false: `cut` is not used) and ptx_view_find_snippets; the arguments are checked */
+static ptx_status view_find_impl(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, bool snip, uint32_t before,
+                                 uint32_t after, ptx_host_result* h, ptx_host_result* cut, ptx_snippets* out) {
+    PTX_HIP(ctx, ptx_enter(ctx));
+    const uint32_t n_logs = v->n_logs;
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status (the host's only: the view keeps the device's) | n_matches | hit_off — what comes down — | the pattern */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), down0 = 2 * st_bytes + a16(no * 8), pat_at = down0, blk0 = pat_at + a16((uint64_t)n_pattern * 2);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, blk0);
+    uint64_t* hit_off = (uint64_t*)(hp0 + 2 * st_bytes);
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t nhits = 0, out_units = 0, out_rows = 0, ot_bytes = 0, os_bytes = 0;
+    bool too_many = false;
+    PtxViewArgs V;
+    memset(&V, 0, sizeof(V));
+    if (e == hipSuccess) {
+        view_text_args(v, V.F.T);
+        V.F.n_matches = (uint32_t*)(d0 + st_bytes);
+        V.F.hit_off = (uint64_t*)(d0 + 2 * st_bytes);
+        V.F.pattern = (const uint16_t*)(d0 + pat_at);
+        V.F.n_pattern = n_pattern;
+        V.F.flags = flags;
+        V.F.cap = max_hits_per_log;
+        V.pre_off = v->pre_off;
+        V.pre = v->pre;
+        V.before = before;
+        V.after = after;
+        if (n_logs) memcpy(hp0, v->h_status.data(), (size_t)n_logs * 4);
+        memcpy(hp0 + pat_at, pattern, (size_t)n_pattern * 2); /* the caller's pattern is free to go */
+        hit_off[0] = 0;                                       /* an empty view: hit_off = {0} */
+    }
+    if (e == hipSuccess && n_logs) {
+        e = hipMemcpyAsync(d0 + pat_at, hp0 + pat_at, (size_t)n_pattern * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_find_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, V.F);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)V.F.n_matches, max_hits_per_log, V.F.hit_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + st_bytes, d0 + st_bytes, down0 - st_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nhits = hit_off[n_logs];
+        if (e == hipSuccess && nhits > 0xFFFFFFFFull) too_many = true, e = hipErrorInvalidValue; /* a lane per listed hit, a slice per hit */
+    }
+    /* block 1, device and pinned host alike: hit_unit | hit_start | hit_end and, for snippets, | elem_start | elem_end | match_unit | unit_off, sspan_off — all of
+     * it comes down in one copy, nothing goes up —; the device's goes on with win_start | win_end | slice_log | first_span | src_off */
+    const uint64_t nso = nhits + 1, col = a16(nhits * 4), oo_at = (snip ? 6 : 3) * col, down1 = oo_at + (snip ? a16(2 * nso * 8) : 0), hblk1 = down1 + 16;
+    const uint64_t ws_at = down1, sl_at = ws_at + 2 * col, src_at = sl_at + 2 * col, dblk1 = snip ? src_at + a16(nhits * 8) + 16 : hblk1;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, hblk1, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    uint64_t* out_off = (uint64_t*)(hp1 + oo_at);
+    if (e == hipSuccess && snip) out_off[0] = out_off[nso] = 0; /* no hits: unit_off = sspan_off = {0} */
+    PtxSliceArgs S;
+    memset(&S, 0, sizeof(S));
+    if (e == hipSuccess && nhits) {
+        e = ptx_dev_malloc((void**)&d1, dblk1);
+        if (e == hipSuccess) {
+            V.n_hits = (uint32_t)nhits;
+            V.F.hit_unit = (uint32_t*)d1;
+            V.F.hit_start = (uint32_t*)(d1 + col);
+            V.F.hit_end = (uint32_t*)(d1 + 2 * col);
+            if (snip) {
+                V.match_unit = (uint32_t*)(d1 + 5 * col);
+                V.win_start = (uint32_t*)(d1 + ws_at);
+                V.win_end = (uint32_t*)(d1 + ws_at + col);
+                S.T = V.F.T;
+                S.slice_off = V.F.hit_off; /* one slice per listed hit, in hit order */
+                S.slice_start = V.win_start;
+                S.slice_end = V.win_end;
+                S.n_slices = (uint32_t)nhits;
+                S.pre_off = v->pre_off;
+                S.pre = v->pre;
+                S.elem_start = (uint32_t*)(d1 + 3 * col);
+                S.elem_end = (uint32_t*)(d1 + 4 * col);
+                S.out_off = (uint64_t*)(d1 + oo_at);
+                S.slice_log = (uint32_t*)(d1 + sl_at);
+                S.first_span = (uint32_t*)(d1 + sl_at + col);
+                S.src_off = (uint64_t*)(d1 + src_at);
+            }
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            const uint32_t grid = (uint32_t)((nhits + 255) / 256);
+            hipLaunchKernelGGL(ptx_view_positions_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, V.F);
+            hipLaunchKernelGGL(ptx_view_locate_kernel, dim3(grid), dim3(256), 0, ctx->stream, V);
+            if (snip) {
+                hipLaunchKernelGGL(ptx_view_windows_kernel, dim3(grid), dim3(256), 0, ctx->stream, V);
+                hipLaunchKernelGGL(ptx_slice_bounds_kernel, dim3(grid), dim3(256), 0, ctx->stream, S);
+                hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, S.out_off, (uint32_t)nhits);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp1, d1, snip ? oo_at + 2 * nso * 8 : 3 * col, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess && snip) {
+            out_units = out_off[nhits];
+            out_rows = out_off[nso + nhits];
+        }
+    }
+    if (e == hipSuccess && snip) e = slice_emit_passes(ctx, S, out_units, out_rows, cut, 0, &ot_bytes, &os_bytes, &ms[2]);
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    if (e != hipSuccess) {
+        if (too_many) return fail(ctx, PTX_ERR_CAPACITY, "more than 2^32 - 1 listed hits: lower max_hits_per_log or the range");
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view find: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->n_pattern = n_pattern;
+    out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->n_slices = snip ? (uint32_t)nhits : 0u;
+    out->status = (const uint32_t*)hp0;
+    out->n_matches = (const uint32_t*)(hp0 + st_bytes);
+    out->hit_off = hit_off;
+    out->hit_unit = (const uint32_t*)hp1;
+    out->hit_start = (const uint32_t*)(hp1 + col);
+    out->hit_end = (const uint32_t*)(hp1 + 2 * col);
+    if (snip) {
+        const uint8_t* hp2 = (const uint8_t*)cut->pinned[0];
+        out->elem_start = (const uint32_t*)(hp1 + 3 * col);
+        out->elem_end = (const uint32_t*)(hp1 + 4 * col);
+        out->match_unit = (const uint32_t*)(hp1 + 5 * col);
+        out->unit_off = out_off;
+        out->sspan_off = out_off + nso;
+        out->text = (const uint16_t*)hp2;
+        out->sspans = (const ptx_span*)(hp2 + ot_bytes);
+        out->sspan_unit = (const uint32_t*)(hp2 + ot_bytes + os_bytes);
+    }
+    return PTX_OK;
+}
+
+static ptx_status view_find_check(ptx_ctx* ctx, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags) {
+    if (!pattern || n_pattern == 0) return fail(ctx, PTX_ERR_INVALID_ARG, "empty pattern");
+    if (n_pattern > PTX_FIND_PATTERN_MAX) return fail(ctx, PTX_ERR_INVALID_ARG, "pattern longer than PTX_FIND_PATTERN_MAX code units");
+    if (flags & ~PTX_FIND_ASCII_NOCASE) return fail(ctx, PTX_ERR_INVALID_ARG, "unknown find flag");
+    return PTX_OK;
+}
+
+ptx_status ptx_view_find_text(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, ptx_matches* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_find_check(ctx, pattern, n_pattern, flags);
+    if (st != PTX_OK) return st;
+    ptx_host_result* h = new ptx_host_result();
+    ptx_snippets m;
+    memset(&m, 0, sizeof(m));
+    st = view_find_impl(ctx, v, pattern, n_pattern, flags, max_hits_per_log, false, 0u, 0u, h, nullptr, &m);
+    if (st != PTX_OK) {
+        delete h;
+        return st;
+    }
+    out->n_logs = m.n_logs;
+    out->n_pattern = m.n_pattern;
+    out->kernel_ms = m.kernel_ms;
+    out->status = m.status;
+    out->n_matches = m.n_matches;
+    out->hit_off = m.hit_off;
+    out->hit_unit = m.hit_unit;
+    out->hit_start = m.hit_start;
+    out->hit_end = m.hit_end;
+    out->owner = h;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_find_snippets(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log, uint32_t before, uint32_t after,
+                                  ptx_snippets* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_find_check(ctx, pattern, n_pattern, flags);
+    if (st != PTX_OK) return st;
+    ptx_host_snippets* h = new ptx_host_snippets();
+    st = view_find_impl(ctx, v, pattern, n_pattern, flags, max_hits_per_log, true, before, after, &h->find, &h->cut, out);
+    if (st != PTX_OK) {
+        delete h;
+        memset(out, 0, sizeof(*out));
+        return st;
+    }
+    out->owner = h;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_text_slices(ptx_ctx* ctx, const ptx_dview* v, const uint64_t* slice_off, const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    const uint32_t n_logs = v->n_logs;
+    if (n_logs && !slice_off) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off is NULL");
+    if (n_logs && slice_off[0] != 0) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off[0] is not 0");
+    for (uint32_t l = 0; l < n_logs; ++l)
+        if (slice_off[l + 1] < slice_off[l]) return fail(ctx, PTX_ERR_INVALID_ARG, "slice_off decreases");
+    const uint64_t ns64 = n_logs ? slice_off[n_logs] : 0;
+    if (ns64 > 0xFFFFFFFFull) return fail(ctx, PTX_ERR_INVALID_ARG, "more than 2^32 - 1 slices");
+    if (ns64 && (!slice_start || !slice_end)) return fail(ctx, PTX_ERR_INVALID_ARG, "slices present but slice_start or slice_end is NULL");
+    const uint32_t ns = (uint32_t)ns64;
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_host_result* h = new ptx_host_result();
+    const uint64_t no = (uint64_t)n_logs + 1, nso = ns64 + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status (the host's only) | elem_start | elem_end | unit_off, sspan_off — what comes down — | slice_off | slice_start |
+     * slice_end — what goes up —; the device's goes on with slice_log | first_span | src_off */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), col = a16(ns64 * 4), es_at = st_bytes, ee_at = es_at + col, oo_at = ee_at + col, down0 = oo_at + a16(2 * nso * 8);
+    const uint64_t so_at = down0, ss_at = so_at + a16(no * 8), se_at = ss_at + col, up_end = se_at + col, hblk0 = up_end + 16;
+    const uint64_t sl_at = up_end, fs_at = sl_at + col, src_at = fs_at + col, dblk0 = src_at + a16(ns64 * 8) + 16;
+    uint8_t *hp0 = nullptr, *d0 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, hblk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess && ns) e = ptx_dev_malloc((void**)&d0, dblk0);
+    uint64_t* out_off = (uint64_t*)(hp0 + oo_at);
+    float ms[2] = {0.f, 0.f};
+    uint64_t out_units = 0, out_rows = 0, ot_bytes = 0, os_bytes = 0;
+    PtxSliceArgs A;
+    memset(&A, 0, sizeof(A));
+    if (e == hipSuccess) {
+        if (n_logs) memcpy(hp0, v->h_status.data(), (size_t)n_logs * 4);
+        out_off[0] = out_off[nso] = 0; /* no slices: unit_off = sspan_off = {0} */
+    }
+    if (e == hipSuccess && ns) {
+        view_text_args(v, A.T);
+        A.slice_off = (const uint64_t*)(d0 + so_at);
+        A.slice_start = (const uint32_t*)(d0 + ss_at);
+        A.slice_end = (const uint32_t*)(d0 + se_at);
+        A.n_slices = ns;
+        A.pre_off = v->pre_off;
+        A.pre = v->pre;
+        A.elem_start = (uint32_t*)(d0 + es_at);
+        A.elem_end = (uint32_t*)(d0 + ee_at);
+        A.out_off = (uint64_t*)(d0 + oo_at);
+        A.slice_log = (uint32_t*)(d0 + sl_at);
+        A.first_span = (uint32_t*)(d0 + fs_at);
+        A.src_off = (uint64_t*)(d0 + src_at);
+        /* the caller's arrays are free to go */
+        memcpy(hp0 + so_at, slice_off, (size_t)no * 8);
+        memcpy(hp0 + ss_at, slice_start, (size_t)ns * 4);
+        memcpy(hp0 + se_at, slice_end, (size_t)ns * 4);
+        e = hipMemcpyAsync(d0 + so_at, hp0 + so_at, up_end - so_at, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_slice_bounds_kernel, dim3((uint32_t)((ns64 + 255) / 256)), dim3(256), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.out_off, ns);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + es_at, d0 + es_at, down0 - es_at, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) {
+            out_units = out_off[ns];
+            out_rows = out_off[nso + ns];
+        }
+    }
+    if (e == hipSuccess) e = slice_emit_passes(ctx, A, out_units, out_rows, h, 1, &ot_bytes, &os_bytes, &ms[1]);
+    (void)ptx_dev_free(d0);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view slices: ") + hipGetErrorString(e));
+    }
+    const uint8_t* hp1 = (const uint8_t*)h->pinned[1];
+    out->n_logs = n_logs;
+    out->n_slices = ns;
+    out->kernel_ms = ms[0] + ms[1];
     out->status = (const uint32_t*)hp0;
     out->elem_start = (const uint32_t*)(hp0 + es_at);
     out->elem_end = (const uint32_t*)(hp0 + ee_at);

@@ -65,6 +65,10 @@ static_assert(sizeof(PtxSliceHdr) == 32u && sizeof(PtxSliceHdr) <= PTX_SLICE_LDS
 
 /* visible elements of log l of the range that a slice can reach: none of a log that has no text */
 PTX_DEV uint32_t ptx_slice_visible(const PtxSliceArgs& A, uint32_t l) {
+    if (A.T.logs == nullptr) { /* a query of a resident view (view_core.h) has no per-log rows: its prefix holds n_visible + 1 words for every good log, none for another */
+        const uint64_t words = A.pre_off[l + 1u] - A.pre_off[l];
+        return words ? (uint32_t)words - 1u : 0u;
+    }
     const uint32_t log = A.T.first_log + l;
     return A.T.status[l] == PTX_OK ? ptx_text_rows(A.T, log, A.T.logs[log].n_visible) : 0u;
 }

@@ -70,6 +70,93 @@ def _copied(ptr, dtype, count):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
 
 
+def _matches_of(m):
+    n, arr = int(m.n_logs), _copied
+    hit_off = arr(m.hit_off, np.uint64, n + 1)
+    nh = int(hit_off[n])
+    return wire.Matches(status=arr(m.status, np.uint32, n), n_matches=arr(m.n_matches, np.uint32, n), hit_off=hit_off, hit_unit=arr(m.hit_unit, np.uint32, nh),
+                        hit_start=arr(m.hit_start, np.uint32, nh), hit_end=arr(m.hit_end, np.uint32, nh), n_pattern=int(m.n_pattern), kernel_ms=float(m.kernel_ms))
+
+
+class TextView:
+    """Engine.text_view's handle: the queries of a resident text view (include/peritext_hip.h "a resident text view")."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.handle = engine, handle
+
+    def _pattern(self, pattern):
+        return np.frombuffer(pattern.encode("utf-16-le", "surrogatepass"), dtype="<u2").astype(np.uint16)
+
+    def info(self):
+        """{n_logs, first_log, n_units, n_prefix_words, bytes, kernel_ms} (ptx_view_info)."""
+        d = abi.ptx_view_desc()
+        self.engine._check(self.engine.lib.ptx_view_info(self.engine.ctx, self.handle, C.byref(d)))
+        return {"n_logs": int(d.n_logs), "first_log": int(d.first_log), "n_units": int(d.n_units), "n_prefix_words": int(d.n_prefix_words), "bytes": int(d.bytes),
+                "kernel_ms": float(d.kernel_ms)}
+
+    def find_text(self, pattern, ascii_nocase=False, max_hits_per_log=0xFFFFFFFF):
+        """Engine.find_text over the view's range (ptx_view_find_text): the same wire.Matches."""
+        eng, pat = self.engine, self._pattern(pattern)
+        m = abi.ptx_matches()
+        eng._check(eng.lib.ptx_view_find_text(eng.ctx, self.handle, pat.ctypes.data_as(abi.u16p), len(pat), abi.FIND_ASCII_NOCASE if ascii_nocase else 0, max_hits_per_log, C.byref(m)))
+        try:
+            return _matches_of(m)
+        finally:
+            eng.lib.ptx_matches_free(C.byref(m))
+
+    def text_slices(self, slices):
+        """Engine.text_slices over the view's range (ptx_view_text_slices): the same wire.Slices."""
+        n_logs = self.info()["n_logs"]
+        if len(slices) != n_logs:
+            raise ValueError("slices holds %d lists for %d logs" % (len(slices), n_logs))
+        off = np.zeros(n_logs + 1, dtype=np.uint64)
+        if n_logs:
+            off[1:] = np.cumsum([len(s) for s in slices], dtype=np.uint64)
+        flat = np.array([p for s in slices for p in s], dtype=np.uint32).reshape(-1, 2)
+        return self.text_slices_flat(off, np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1]))
+
+    def text_slices_flat(self, slice_off, slice_start, slice_end):
+        """text_slices with the C ABI's own arrays (numpy; None passes NULL)."""
+        eng = self.engine
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None and len(a) else C.cast(None, t)  # noqa: E731
+        m = abi.ptx_slices()
+        eng._check(eng.lib.ptx_view_text_slices(eng.ctx, self.handle, ptr(slice_off, abi.u64p), ptr(slice_start, abi.u32p), ptr(slice_end, abi.u32p), C.byref(m)))
+        try:
+            n, k, arr = int(m.n_logs), int(m.n_slices), _copied
+            unit_off, sspan_off = arr(m.unit_off, np.uint64, k + 1), arr(m.sspan_off, np.uint64, k + 1)
+            nr = int(sspan_off[k])
+            return wire.Slices(status=arr(m.status, np.uint32, n), slice_off=np.array(slice_off, dtype=np.uint64) if n else np.zeros(1, np.uint64),
+                               elem_start=arr(m.elem_start, np.uint32, k), elem_end=arr(m.elem_end, np.uint32, k), unit_off=unit_off,
+                               text=arr(m.text, np.uint16, int(unit_off[k])), sspan_off=sspan_off, sspans=arr(m.sspans, abi.SPAN_DTYPE, nr),
+                               sspan_unit=arr(m.sspan_unit, np.uint32, nr), kernel_ms=float(m.kernel_ms))
+        finally:
+            eng.lib.ptx_slices_free(C.byref(m))
+
+    def find_snippets(self, pattern, before=0, after=0, ascii_nocase=False, max_hits_per_log=0xFFFFFFFF):
+        """find_text, and for every listed hit the text and the span rows of the elements [hit_start - before, hit_end + after) with the match's offset inside
+        that text, in one call that keeps the hits on the device (ptx_view_find_snippets): wire.Snippets."""
+        eng, pat = self.engine, self._pattern(pattern)
+        m = abi.ptx_snippets()
+        eng._check(eng.lib.ptx_view_find_snippets(eng.ctx, self.handle, pat.ctypes.data_as(abi.u16p), len(pat), abi.FIND_ASCII_NOCASE if ascii_nocase else 0, max_hits_per_log,
+                                                  before, after, C.byref(m)))
+        try:
+            n, k, arr = int(m.n_logs), int(m.n_slices), _copied
+            unit_off, sspan_off = arr(m.unit_off, np.uint64, k + 1), arr(m.sspan_off, np.uint64, k + 1)
+            nr = int(sspan_off[k])
+            return wire.Snippets(status=arr(m.status, np.uint32, n), slice_off=arr(m.hit_off, np.uint64, n + 1), elem_start=arr(m.elem_start, np.uint32, k),
+                                 elem_end=arr(m.elem_end, np.uint32, k), unit_off=unit_off, text=arr(m.text, np.uint16, int(unit_off[k])), sspan_off=sspan_off,
+                                 sspans=arr(m.sspans, abi.SPAN_DTYPE, nr), sspan_unit=arr(m.sspan_unit, np.uint32, nr), kernel_ms=float(m.kernel_ms),
+                                 n_matches=arr(m.n_matches, np.uint32, n), hit_unit=arr(m.hit_unit, np.uint32, k), hit_start=arr(m.hit_start, np.uint32, k),
+                                 hit_end=arr(m.hit_end, np.uint32, k), match_unit=arr(m.match_unit, np.uint32, k), n_pattern=int(m.n_pattern))
+        finally:
+            eng.lib.ptx_snippets_free(C.byref(m))
+
+    def free(self):
+        if self.handle is not None:
+            self.engine.lib.ptx_text_view_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+
 class Engine:
     """One device context (one HIP stream).  One Engine per process/GPU in multi-GPU runs."""
 
@@ -407,6 +494,16 @@ class Engine:
                                sspan_unit=arr(m.sspan_unit, np.uint32, nr), kernel_ms=float(m.kernel_ms))
         finally:
             self.lib.ptx_slices_free(C.byref(m))
+
+    def text_view(self, dbatch, dresult, dstrings, first_log=0, n_logs=None):
+        """A resident text view of the logs [first_log, first_log + n_logs) of one merge (ptx_text_view_create): the assembled text and the element prefix stay on
+        the device, and TextView.find_text / text_slices / find_snippets query them any number of times without a text or prefix pass.  `dstrings` (and the
+        batch) may be freed once this returns; `dresult` must outlive the view and stay the merge it was made from.  Free it with TextView.free()."""
+        if n_logs is None:
+            n_logs = self.n_logs(dbatch) - first_log
+        h = C.c_void_p()
+        self._check(self.lib.ptx_text_view_create(self.ctx, dbatch, dresult, dstrings, first_log, n_logs, C.byref(h)))
+        return TextView(self, h)
 
     def replay_patches(self, dbatch, dresult, first_row=None):
         """The Patch[] stream every applyChange of every log would have returned (reference/src/micromerge.ts:499),

@@ -95,6 +95,13 @@ struct Lib {
     /* the text and span rows of element ranges */
     ptx_status (*result_text_slices)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, const uint64_t*, const uint32_t*, const uint32_t*, ptx_slices*) = nullptr;
     void (*slices_free)(ptx_slices*) = nullptr;
+    /* a resident text view: many searches and snippets against one merge */
+    ptx_status (*text_view_create)(ptx_ctx*, const ptx_dbatch*, const ptx_dresult*, const ptx_dstrings*, uint32_t, uint32_t, ptx_dview**) = nullptr;
+    void (*text_view_free)(ptx_ctx*, ptx_dview*) = nullptr;
+    ptx_status (*view_find_text)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, uint32_t, ptx_matches*) = nullptr;
+    ptx_status (*view_text_slices)(ptx_ctx*, const ptx_dview*, const uint64_t*, const uint32_t*, const uint32_t*, ptx_slices*) = nullptr;
+    ptx_status (*view_find_snippets)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, ptx_snippets*) = nullptr;
+    void (*snippets_free)(ptx_snippets*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -145,7 +152,9 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.sync_replicas, "ptx_sync_replicas") && sym(L.accumulate_patches, "ptx_accumulate_patches") && sym(L.check_patches, "ptx_check_patches") &&
                   sym(L.batch_at_versions, "ptx_batch_at_versions") && sym(L.strings_upload, "ptx_strings_upload") && sym(L.strings_free, "ptx_strings_free") &&
                   sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free") && sym(L.result_find_text, "ptx_result_find_text") &&
-                  sym(L.matches_free, "ptx_matches_free") && sym(L.result_text_slices, "ptx_result_text_slices") && sym(L.slices_free, "ptx_slices_free");
+                  sym(L.matches_free, "ptx_matches_free") && sym(L.result_text_slices, "ptx_result_text_slices") && sym(L.slices_free, "ptx_slices_free") &&
+                  sym(L.text_view_create, "ptx_text_view_create") && sym(L.text_view_free, "ptx_text_view_free") && sym(L.view_find_text, "ptx_view_find_text") &&
+                  sym(L.view_text_slices, "ptx_view_text_slices") && sym(L.view_find_snippets, "ptx_view_find_snippets") && sym(L.snippets_free, "ptx_snippets_free");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -735,6 +744,181 @@ napi_value TextSlices(napi_env env, napi_callback_info info) {
         if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
     }
     L.slices_free(&m);
+    return out;
+}
+
+/* ---- a resident text view (INTEGRATION.md "Many searches against one merge"): viewCreate(ctx, batch, strings) uploads and merges, makes a view of every log
+ *      (ptx_text_view_create) and returns the merge's compact rows (as applyMaterialize: the comment intervals resolve a row's comment ids) + {handle}.  The batch
+ *      is freed before it returns and the strings may be freed by the caller: the handle keeps the merge's result and the view.  viewFindText(ctx, handle,
+ *      pattern, flags, maxHitsPerLog) -> findText's object; viewTextSlices(ctx, handle, sliceOff, sliceStart, sliceEnd) -> textSlices' slice arrays;
+ *      viewFindSnippets(ctx, handle, pattern, flags, maxHitsPerLog, before, after) -> both, the slices being one per listed hit (their sliceOff IS hitOff), and
+ *      matchUnit: Uint32Array; viewFree(ctx, handle) ---- */
+struct ViewHandle {
+    ptx_dresult* dr = nullptr;
+    ptx_dview* view = nullptr;
+    uint32_t n_logs = 0;
+};
+static ViewHandle* view_of(napi_env env, napi_value v) {
+    void* p = nullptr;
+    if (napi_get_value_external(env, v, &p) != napi_ok) return nullptr;
+    ViewHandle* h = (ViewHandle*)p;
+    return h && h->view ? h : nullptr;
+}
+static bool pattern_arg(napi_env env, napi_value v, const uint16_t** pat, uint32_t* n) {
+    static const uint16_t none = 0; /* (a zero-length typed array may come without storage: the library answers n_pattern == 0 itself) */
+    void* data = nullptr;
+    size_t len = 0;
+    if (!typed_arg(env, v, napi_uint16_array, &data, &len) || len > 0xFFFFFFFFull) return false;
+    *pat = len ? (const uint16_t*)data : &none;
+    *n = (uint32_t)len;
+    return true;
+}
+static void hits_to_js(napi_env env, napi_value out, const uint32_t* status, const uint32_t* n_matches, const uint64_t* hit_off, const uint32_t* hit_unit, const uint32_t* hit_start,
+                       const uint32_t* hit_end, size_t nl) {
+    const size_t nh = (size_t)hit_off[nl];
+    napi_value v;
+    if ((v = make_u32(env, status, nl))) napi_set_named_property(env, out, "status", v);
+    if ((v = make_u32(env, n_matches, nl))) napi_set_named_property(env, out, "nMatches", v);
+    if ((v = make_typed(env, napi_biguint64_array, 8, hit_off, nl + 1))) napi_set_named_property(env, out, "hitOff", v);
+    if ((v = make_u32(env, hit_unit, nh))) napi_set_named_property(env, out, "hitUnit", v);
+    if ((v = make_u32(env, hit_start, nh))) napi_set_named_property(env, out, "hitStart", v);
+    if ((v = make_u32(env, hit_end, nh))) napi_set_named_property(env, out, "hitEnd", v);
+}
+static void cut_to_js(napi_env env, napi_value out, const uint32_t* status, size_t nl, size_t ns, const uint32_t* elem_start, const uint32_t* elem_end, const uint64_t* unit_off,
+                      const uint64_t* sspan_off, const uint16_t* text, const ptx_span* sspans, const uint32_t* sspan_unit) {
+    const size_t nu = (size_t)unit_off[ns], nr = (size_t)sspan_off[ns];
+    napi_value v;
+    if ((v = make_u32(env, status, nl))) napi_set_named_property(env, out, "sliceStatus", v);
+    if ((v = make_u32(env, elem_start, ns))) napi_set_named_property(env, out, "elemStart", v);
+    if ((v = make_u32(env, elem_end, ns))) napi_set_named_property(env, out, "elemEnd", v);
+    if ((v = make_typed(env, napi_biguint64_array, 8, unit_off, ns + 1))) napi_set_named_property(env, out, "unitOff", v);
+    if ((v = make_typed(env, napi_biguint64_array, 8, sspan_off, ns + 1))) napi_set_named_property(env, out, "sspanOff", v);
+    if ((v = make_typed(env, napi_uint16_array, 2, text, nu))) napi_set_named_property(env, out, "sliceText", v);
+    if ((v = make_u32(env, sspans, 2 * nr))) napi_set_named_property(env, out, "sspans", v);
+    if ((v = make_u32(env, sspan_unit, nr))) napi_set_named_property(env, out, "sspanUnit", v);
+}
+napi_value ViewCreate(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 2 ? ctx_of(env, argv[0]) : nullptr;
+    ptx_dstrings* ds = ctx ? strings_of(env, argv[2]) : nullptr;
+    if (!ds) return throw_msg(env, "viewCreate(ctx, batch, strings)");
+    ptx_batch pb;
+    if (!read_batch(env, argv[1], &pb)) return nullptr;
+    ptx_dbatch* db = nullptr;
+    ViewHandle* h = new ViewHandle();
+    h->n_logs = pb.n_logs;
+    ptx_result res;
+    bool have_res = false;
+    ptx_status st = L.batch_upload(ctx, &pb, &db);
+    if (st == PTX_OK) st = L.result_alloc(ctx, db, &h->dr);
+    if (st == PTX_OK) st = L.merge(ctx, db, h->dr);
+    if (st == PTX_OK) st = L.result_download(ctx, db, h->dr, &res);
+    have_res = st == PTX_OK;
+    if (st == PTX_OK) st = L.text_view_create(ctx, db, h->dr, ds, 0, pb.n_logs, &h->view);
+    std::string err = st != PTX_OK ? L.last_error(ctx) : "";
+    if (db) L.batch_free(ctx, db); /* the view reads nothing of the batch */
+    napi_value out = st == PTX_OK ? result_to_js(env, res, nullptr) : nullptr, ext;
+    if (st != PTX_OK && have_res) L.result_free(&res);
+    if (out && napi_create_external(env, h, nullptr, nullptr, &ext) == napi_ok && napi_set_named_property(env, out, "handle", ext) == napi_ok) return out;
+    if (h->view) L.text_view_free(ctx, h->view);
+    if (h->dr) L.dresult_free(ctx, h->dr);
+    delete h;
+    if (st != PTX_OK) {
+        char msg[1024];
+        snprintf(msg, sizeof(msg), "viewCreate (ptx_merge / ptx_text_view_create) failed (status %d): %s", st, err.c_str());
+        return throw_msg(env, msg);
+    }
+    return out;
+}
+napi_value ViewFree(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 1 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (h && L.handle) { /* the record itself stays (a second viewFree, or a query after it, finds no view and does nothing) */
+        L.text_view_free(ctx, h->view);
+        L.dresult_free(ctx, h->dr);
+        h->view = nullptr;
+        h->dr = nullptr;
+    }
+    return nullptr;
+}
+napi_value ViewFindText(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 4 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewFindText(ctx, handle, pattern: Uint16Array, flags, maxHitsPerLog): no live view");
+    const uint16_t* pat = nullptr;
+    uint32_t np = 0, flags = 0, cap = 0;
+    if (!pattern_arg(env, argv[2], &pat, &np) || napi_get_value_uint32(env, argv[3], &flags) != napi_ok || napi_get_value_uint32(env, argv[4], &cap) != napi_ok)
+        return throw_msg(env, "viewFindText: pattern must be a Uint16Array, flags and maxHitsPerLog unsigned 32-bit numbers");
+    ptx_matches m;
+    const ptx_status st = L.view_find_text(ctx, h->view, pat, np, flags, cap, &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_find_text", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        hits_to_js(env, out, m.status, m.n_matches, m.hit_off, m.hit_unit, m.hit_start, m.hit_end, (size_t)m.n_logs);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.matches_free(&m);
+    return out;
+}
+napi_value ViewTextSlices(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 4 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewTextSlices(ctx, handle, sliceOff: BigUint64Array, sliceStart: Uint32Array, sliceEnd: Uint32Array): no live view");
+    void *off = nullptr, *start = nullptr, *end = nullptr;
+    size_t n_off = 0, n_start = 0, n_end = 0;
+    if (!typed_arg(env, argv[2], napi_biguint64_array, &off, &n_off) || !typed_arg(env, argv[3], napi_uint32_array, &start, &n_start) || !typed_arg(env, argv[4], napi_uint32_array, &end, &n_end))
+        return throw_msg(env, "viewTextSlices: sliceOff must be a BigUint64Array, sliceStart and sliceEnd Uint32Arrays");
+    if (n_off != (size_t)h->n_logs + 1 || n_start != n_end || ((const uint64_t*)off)[h->n_logs] != n_start)
+        return throw_msg(env, "viewTextSlices: sliceOff holds nLogs + 1 offsets, the last one the length of sliceStart and sliceEnd");
+    ptx_slices m;
+    const ptx_status st = L.view_text_slices(ctx, h->view, (const uint64_t*)off, n_start ? (const uint32_t*)start : nullptr, n_start ? (const uint32_t*)end : nullptr, &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_text_slices", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        cut_to_js(env, out, m.status, (size_t)m.n_logs, (size_t)m.n_slices, m.elem_start, m.elem_end, m.unit_off, m.sspan_off, m.text, m.sspans, m.sspan_unit);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.slices_free(&m);
+    return out;
+}
+napi_value ViewFindSnippets(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 6 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewFindSnippets(ctx, handle, pattern: Uint16Array, flags, maxHitsPerLog, before, after): no live view");
+    const uint16_t* pat = nullptr;
+    uint32_t np = 0, flags = 0, cap = 0, before = 0, after = 0;
+    if (!pattern_arg(env, argv[2], &pat, &np) || napi_get_value_uint32(env, argv[3], &flags) != napi_ok || napi_get_value_uint32(env, argv[4], &cap) != napi_ok ||
+        napi_get_value_uint32(env, argv[5], &before) != napi_ok || napi_get_value_uint32(env, argv[6], &after) != napi_ok)
+        return throw_msg(env, "viewFindSnippets: pattern must be a Uint16Array, flags, maxHitsPerLog, before and after unsigned 32-bit numbers");
+    ptx_snippets m;
+    const ptx_status st = L.view_find_snippets(ctx, h->view, pat, np, flags, cap, before, after, &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_find_snippets", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        hits_to_js(env, out, m.status, m.n_matches, m.hit_off, m.hit_unit, m.hit_start, m.hit_end, (size_t)m.n_logs);
+        cut_to_js(env, out, m.status, (size_t)m.n_logs, (size_t)m.n_slices, m.elem_start, m.elem_end, m.unit_off, m.sspan_off, m.text, m.sspans, m.sspan_unit);
+        if ((v = make_u32(env, m.match_unit, (size_t)m.n_slices))) napi_set_named_property(env, out, "matchUnit", v);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.snippets_free(&m);
     return out;
 }
 
@@ -1351,7 +1535,12 @@ napi_value Init(napi_env env, napi_value exports) {
                                               {"stringsFree", nullptr, StringsFree, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"resultText", nullptr, ResultText, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"findText", nullptr, FindText, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"textSlices", nullptr, TextSlices, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"textSlices", nullptr, TextSlices, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewCreate", nullptr, ViewCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewFree", nullptr, ViewFree, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewFindText", nullptr, ViewFindText, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewTextSlices", nullptr, ViewTextSlices, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewFindSnippets", nullptr, ViewFindSnippets, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

@@ -108,6 +108,13 @@ export type JsonValue = string | number | boolean | null | JsonValue[] | { [key:
 /** ptx_root_map's raw answer (include/peritext_hip.h ptx_root_maps) */
 export interface WireRootMaps { entryOff: BigUint64Array; logs: Uint32Array; entries: Uint32Array }
 
+export interface Snippet { log: number; hitStart: number; hitEnd: number; text: string; matchUnit: number; spans: FormatSpanWithText[] }
+export interface TextView {
+    findText(needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number }): Array<Array<{ status: number; count: number; hits: Array<{ unit: number; startIndex: number; endIndex: number }> }>>
+    textSlices(ranges: Array<Array<Array<{ startIndex: number; endIndex: number }>>>): Array<Array<Array<{ status: number; startIndex: number; endIndex: number; spans: FormatSpanWithText[] }>>>
+    findSnippets(needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number; before?: number; after?: number }): Array<Array<{ status: number; count: number; snippets: Snippet[] }>>
+    free(): void
+}
 export class MergeEngine {
     /** resident (default true): the logs of a document's replica() handles stay in HBM between calls — a read encodes and uploads only the Changes that
      *  arrived since (ptx_batch_append), merges the resident logs and fetches the Patch[] records of the new rows only (ptx_replay_patches_from).
@@ -128,6 +135,10 @@ export class MergeEngine {
      *  Array.prototype.slice's clamping for non-negative indexes; a replica's ranges may come in any order, overlap and repeat; per range, in that order, the range
      *  after clamping and the FormatSpanWithText[] of its elements */
     textSlices(docs: Change[][][], ranges: Array<Array<Array<{ startIndex: number; endIndex: number }>>>, opts?: {}): Array<Array<Array<{ status: number; startIndex: number; endIndex: number; spans: FormatSpanWithText[] }>>>
+    /** A resident text view of every replica of `docs` (ptx_text_view_create): merged once, the text and the element prefix stay on the device; search and cut any
+     *  number of times, then free().  findText and textSlices return what the engine's methods of the same name return; findSnippets finds and cuts in one device
+     *  call: per listed hit the elements [hitStart - before, hitEnd + after), `text.substr(matchUnit, needle.length)` being the match. */
+    textView(docs: Change[][][]): TextView
     /** spans as applyChanges + patches[doc][replica][change] = what applyChange(change) returns (micromerge.ts:499) */
     applyChangesWithPatches(docs: Change[][][]): { spans: FormatSpanWithText[][][]; patches: Patch[][][][] }
     /** patch streams (patchOff / patchLogs / patches of `res`: this library's, or a peer's) back into the documents they describe (ptx_accumulate_patches) */

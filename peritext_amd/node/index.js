@@ -763,6 +763,51 @@ function decodePatches(batch, res, log) {
     return out
 }
 
+
+/** a needle as UTF-16 code units, not code points: a lone surrogate is a legal needle */
+function patternOf(needle) {
+    const pattern = new Uint16Array(needle.length)
+    for (let i = 0; i < needle.length; i++) pattern[i] = needle.charCodeAt(i)
+    return pattern
+}
+/** { status, count, hits } of log l of a find answer (findText, viewFindText) */
+function hitsOfLog(m, l) {
+    const hits = []
+    for (let k = Number(m.hitOff[l]); k < Number(m.hitOff[l + 1]); k++) hits.push({ unit: m.hitUnit[k], startIndex: m.hitStart[k], endIndex: m.hitEnd[k] })
+    return { status: m.status[l], count: m.nMatches[l], hits }
+}
+/** ranges[doc][replica] = [{ startIndex, endIndex }] as the C ABI's flat arrays, in document-major order */
+function flatRanges(docs, ranges) {
+    let nLogs = 0
+    docs.forEach(logs => { nLogs += logs.length })
+    const off = new BigUint64Array(nLogs + 1)
+    const flat = []
+    let log = 0
+    if (!Array.isArray(ranges) || ranges.length !== docs.length) throw new RangeError("ranges: one entry per document")
+    docs.forEach((logs, d) => {
+        if (!Array.isArray(ranges[d]) || ranges[d].length !== logs.length) throw new RangeError("ranges[" + d + "]: one entry per replica")
+        logs.forEach((_, r) => {
+            for (const x of ranges[d][r]) {
+                if (!Number.isInteger(x.startIndex) || !Number.isInteger(x.endIndex) || x.startIndex < 0 || x.endIndex < 0 || x.startIndex > 0xFFFFFFFF || x.endIndex > 0xFFFFFFFF)
+                    throw new RangeError("ranges: startIndex and endIndex are unsigned 32-bit integers")
+                flat.push(x)
+            }
+            off[++log] = BigInt(flat.length)
+        })
+    })
+    return { off, start: Uint32Array.from(flat, x => x.startIndex), end: Uint32Array.from(flat, x => x.endIndex) }
+}
+/** { text, spans: FormatSpanWithText[] } of slice k (of log l) of a slice answer `m`; `rows` = the merge's compact rows of the same batch (comment intervals) */
+function sliceOf(batch, rows, m, l, k) {
+    const bc = Number(rows.cintOff[l]), nCints = rows.logs[12 * l + 5], comments = batch.docComments[batch.logDoc[l]]
+    const u0 = Number(m.unitOff[k]), u1 = Number(m.unitOff[k + 1]), r0 = Number(m.sspanOff[k]), r1 = Number(m.sspanOff[k + 1])
+    const text = Buffer.from(m.sliceText.buffer, m.sliceText.byteOffset + 2 * u0, 2 * (u1 - u0)).toString("utf16le")
+    const spans = []
+    for (let q = r0; q < r1; q++)
+        spans.push({ text: text.slice(m.sspanUnit[q], q + 1 < r1 ? m.sspanUnit[q + 1] : u1 - u0), marks: spanMarks(batch, rows, m.sspans[2 * q + 1], m.sspans[2 * q], bc, nCints, comments) })
+    return { text, spans }
+}
+
 class MergeEngine {
     /** opts: {device?: number, libPath?: string, addonPath?: string, resident?: boolean} */
     constructor(opts) {
@@ -901,16 +946,11 @@ class MergeEngine {
         if (typeof needle !== "string" || needle.length === 0 || needle.length > FIND_PATTERN_MAX) throw new RangeError("needle: a string of 1 .. " + FIND_PATTERN_MAX + " UTF-16 code units")
         const maxHits = opts && opts.maxHits !== undefined ? opts.maxHits : 0xFFFFFFFF
         if (!Number.isInteger(maxHits) || maxHits < 0 || maxHits > 0xFFFFFFFF) throw new RangeError("maxHits: an unsigned 32-bit integer")
-        const pattern = new Uint16Array(needle.length) /* code units, not code points: a lone surrogate is a legal needle */
-        for (let i = 0; i < needle.length; i++) pattern[i] = needle.charCodeAt(i)
+        const pattern = patternOf(needle)
         const batch = encodeDocs(docs)
         const m = this._withStrings(batch, strings => this.addon.findText(this.ctx, batch, strings, pattern, opts && opts.ignoreAsciiCase ? FIND_ASCII_NOCASE : 0, maxHits))
         let log = 0
-        return docs.map(logs => logs.map(() => {
-            const l = log++, hits = []
-            for (let k = Number(m.hitOff[l]); k < Number(m.hitOff[l + 1]); k++) hits.push({ unit: m.hitUnit[k], startIndex: m.hitStart[k], endIndex: m.hitEnd[k] })
-            return { status: m.status[l], count: m.nMatches[l], hits }
-        }))
+        return docs.map(logs => logs.map(() => hitsOfLog(m, log++)))
     }
     /** The text, with its formatting, of element ranges of every replica, cut on the device without downloading the documents' text (ptx_result_text_slices):
      *  encode, upload, merge and cut in one call.  ranges[doc][replica] = Array<{ startIndex, endIndex }> of visible element indexes with
@@ -920,41 +960,79 @@ class MergeEngine {
      *  and empty ranges. */
     textSlices(docs, ranges, opts) {
         const batch = encodeDocs(docs)
-        const nLogs = batch.logOff.length - 1
-        const off = new BigUint64Array(nLogs + 1)
-        const flat = []
-        let log = 0
-        if (!Array.isArray(ranges) || ranges.length !== docs.length) throw new RangeError("ranges: one entry per document")
-        docs.forEach((logs, d) => {
-            if (!Array.isArray(ranges[d]) || ranges[d].length !== logs.length) throw new RangeError("ranges[" + d + "]: one entry per replica")
-            logs.forEach((_, r) => {
-                for (const x of ranges[d][r]) {
-                    if (!Number.isInteger(x.startIndex) || !Number.isInteger(x.endIndex) || x.startIndex < 0 || x.endIndex < 0 || x.startIndex > 0xFFFFFFFF || x.endIndex > 0xFFFFFFFF)
-                        throw new RangeError("ranges: startIndex and endIndex are unsigned 32-bit integers")
-                    flat.push(x)
-                }
-                off[++log] = BigInt(flat.length)
-            })
-        })
-        const start = Uint32Array.from(flat, x => x.startIndex), end = Uint32Array.from(flat, x => x.endIndex)
+        const { off, start, end } = flatRanges(docs, ranges)
         const m = this._withStrings(batch, strings => this.addon.textSlices(this.ctx, batch, strings, off, start, end))
-        log = 0
+        let log = 0
         return docs.map(logs => logs.map(() => {
             const l = log++, out = []
             const st = m.logs[12 * l] || m.sliceStatus[l]
-            const bc = Number(m.cintOff[l]), nCints = m.logs[12 * l + 5], comments = batch.docComments[batch.logDoc[l]]
-            for (let k = Number(off[l]); k < Number(off[l + 1]); k++) {
-                const u0 = Number(m.unitOff[k]), u1 = Number(m.unitOff[k + 1]), r0 = Number(m.sspanOff[k]), r1 = Number(m.sspanOff[k + 1])
-                const whole = Buffer.from(m.sliceText.buffer, m.sliceText.byteOffset + 2 * u0, 2 * (u1 - u0)).toString("utf16le")
-                const spans = []
-                for (let q = r0; q < r1; q++) {
-                    const text = whole.slice(m.sspanUnit[q], q + 1 < r1 ? m.sspanUnit[q + 1] : u1 - u0)
-                    spans.push({ text, marks: spanMarks(batch, m, m.sspans[2 * q + 1], m.sspans[2 * q], bc, nCints, comments) })
-                }
-                out.push({ status: st, startIndex: m.elemStart[k], endIndex: m.elemEnd[k], spans })
-            }
+            for (let k = Number(off[l]); k < Number(off[l + 1]); k++) out.push({ status: st, startIndex: m.elemStart[k], endIndex: m.elemEnd[k], spans: sliceOf(batch, m, m, l, k).spans })
             return out
         }))
+    }
+    /** A resident text view of every replica of `docs` (ptx_text_view_create): encode, upload and merge ONCE, keep the assembled text and the element prefix on
+     *  the device, then search and cut any number of times without a text pass per call.  The string table goes up for the creation only.  Returns
+     *    findText(needle, opts)      what MergeEngine.findText returns for the same documents
+     *    textSlices(ranges)          what MergeEngine.textSlices returns
+     *    findSnippets(needle, opts)  find, and per listed hit the text and formatting of the elements [hitStart - opts.before, hitEnd + opts.after) (both
+     *                                default 0; clamped as Array.prototype.slice clamps) in ONE device call: per document and replica { status, count, snippets },
+     *                                a snippet being { log, hitStart, hitEnd, text, matchUnit, spans } — text.substr(matchUnit, needle.length) is the match (highlight
+     *                                it), spans the FormatSpanWithText[] of the snippet.  opts.ignoreAsciiCase and opts.maxHits as findText
+     *    free()                      releases the device memory; the view is unusable afterwards */
+    textView(docs) {
+        const batch = encodeDocs(docs)
+        const rows = this._withStrings(batch, strings => this.addon.viewCreate(this.ctx, batch, strings))
+        const engine = this
+        let handle = rows.handle
+        const live = () => {
+            if (handle === null) throw new Error("textView: the view has been freed")
+            return handle
+        }
+        const findArgs = (needle, opts) => {
+            if (typeof needle !== "string" || needle.length === 0 || needle.length > FIND_PATTERN_MAX) throw new RangeError("needle: a string of 1 .. " + FIND_PATTERN_MAX + " UTF-16 code units")
+            const u32 = (name, dflt) => {
+                const v = opts && opts[name] !== undefined ? opts[name] : dflt
+                if (!Number.isInteger(v) || v < 0 || v > 0xFFFFFFFF) throw new RangeError(name + ": an unsigned 32-bit integer")
+                return v
+            }
+            return { pattern: patternOf(needle), flags: opts && opts.ignoreAsciiCase ? FIND_ASCII_NOCASE : 0, maxHits: u32("maxHits", 0xFFFFFFFF), before: u32("before", 0), after: u32("after", 0) }
+        }
+        return {
+            findText(needle, opts) {
+                const a = findArgs(needle, opts)
+                const m = engine.addon.viewFindText(engine.ctx, live(), a.pattern, a.flags, a.maxHits)
+                let log = 0
+                return docs.map(logs => logs.map(() => hitsOfLog(m, log++)))
+            },
+            textSlices(ranges) {
+                const { off, start, end } = flatRanges(docs, ranges)
+                const m = engine.addon.viewTextSlices(engine.ctx, live(), off, start, end)
+                let log = 0
+                return docs.map(logs => logs.map(() => {
+                    const l = log++, out = []
+                    const st = rows.logs[12 * l] || m.sliceStatus[l]
+                    for (let k = Number(off[l]); k < Number(off[l + 1]); k++) out.push({ status: st, startIndex: m.elemStart[k], endIndex: m.elemEnd[k], spans: sliceOf(batch, rows, m, l, k).spans })
+                    return out
+                }))
+            },
+            findSnippets(needle, opts) {
+                const a = findArgs(needle, opts)
+                const m = engine.addon.viewFindSnippets(engine.ctx, live(), a.pattern, a.flags, a.maxHits, a.before, a.after)
+                let log = 0
+                return docs.map(logs => logs.map(() => {
+                    const l = log++, snippets = []
+                    for (let k = Number(m.hitOff[l]); k < Number(m.hitOff[l + 1]); k++) {
+                        const cut = sliceOf(batch, rows, m, l, k)
+                        snippets.push({ log: l, hitStart: m.hitStart[k], hitEnd: m.hitEnd[k], text: cut.text, matchUnit: m.matchUnit[k], spans: cut.spans })
+                    }
+                    return { status: m.status[l], count: m.nMatches[l], snippets }
+                }))
+            },
+            free() {
+                if (handle !== null) engine.addon.viewFree(engine.ctx, handle)
+                handle = null
+            },
+        }
     }
     /** Per-document digests (2 x u64 as BigInt pairs) of every log: equal digests <=> deep-equal spans. */
     digests(docs) {

@@ -872,6 +872,34 @@ class Slices:
         return [(int(self.sspans[r]["start"]), int(self.sspans[r]["attr"]), int(self.sspan_unit[r])) for r in range(a, b)]
 
 
+@dataclass
+class Snippets(Slices):
+    """Host view of ptx_snippets (TextView.find_snippets): a find and one slice per listed hit, in hit order — slice_off IS hit_off.  Every field of Matches and of
+    Slices (the slice of hit k is [hit_start[k] - before, hit_end[k] + after), saturated and clamped), and match_unit[k]: the code-unit offset of the match
+    within snippet k's text, hit_unit[k] minus the unit offset of element elem_start[k].  decode_slice_spans takes it as it takes a Slices."""
+
+    n_matches: np.ndarray = None  # u32 [n_logs]
+    hit_unit: np.ndarray = None  # u32 [n_slices]
+    hit_start: np.ndarray = None
+    hit_end: np.ndarray = None
+    match_unit: np.ndarray = None  # u32 [n_slices]
+    n_pattern: int = 0
+
+    @property
+    def hit_off(self):
+        return self.slice_off
+
+    def matches(self):
+        """The find half as a Matches."""
+        return Matches(status=self.status, n_matches=self.n_matches, hit_off=self.slice_off, hit_unit=self.hit_unit, hit_start=self.hit_start, hit_end=self.hit_end,
+                       n_pattern=self.n_pattern, kernel_ms=self.kernel_ms)
+
+    def of_log(self, log):
+        """[(unit, start_index, end_index, snippet text, match_unit)] of one log's listed hits."""
+        a, b = int(self.slice_off[log]), int(self.slice_off[log + 1])
+        return [(int(self.hit_unit[k]), int(self.hit_start[k]), int(self.hit_end[k]), self.of_slice(k), int(self.match_unit[k])) for k in range(a, b)]
+
+
 def decode_slice_spans(batch, res, slices, log, j):
     """FormatSpanWithText[] of slice j of log `log`: what cutting decode_spans_text's result down to the slice's elements gives — every row's text ONE slice of
     the slice's text, comment ids resolved against `res`'s cintervals at the row's (document) start.  `res` and `slices` cover the same range of logs."""
