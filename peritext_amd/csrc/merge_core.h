@@ -76,6 +76,16 @@
 #ifndef PTX_MARK_OPS_FORM
 #define PTX_MARK_OPS_FORM 1 /* which bodies hold P5a's second form, the one that reads a resident log's operand words (an expression over the body's template parameters; 0: the gathers alone) */
 #endif
+#ifndef PTX_ORDER_CHECKS_ONCE_FORM
+/* which bodies may skip a standing log's row-order checks (an expression over the body's template parameters, only where P5a's second form is): the three-wave
+ * lean build, where it was measured.  Every other body compiles to what it was */
+#define PTX_ORDER_CHECKS_ONCE_FORM (kLean && kThreads == 192u)
+#endif
+/* one row-order check of P3a / P3b is made (per delete of the pass behind P3a, per insert of P3b): counted by the CPU test-suite's driver of the skip, nothing
+ * anywhere else */
+#ifndef PTX_NOTE_ORDER_CHECK
+#define PTX_NOTE_ORDER_CHECK() ((void)0)
+#endif
 #ifndef PTX_UB64
 #define PTX_UB64 1u
 #endif
@@ -172,6 +182,9 @@ struct PtxMergeArgs {
      * operands through its row, as before.  The launch that writes the index writes them; a launch that reads the index reads those of the logs whose word stands */
     uint64_t* mark_ops;       /* optional: one word per mark op, log l from word ptx_row_index_off(row offset, l) */
     uint32_t* mark_ops_stand; /* with it [n_logs]: N once the operand words of all the log's mark ops stand, else 0 */
+    /* the host's leave to take a standing log's row-order checks as passed (see where ops_rd is derived): set in launches that read the operand words, 0 = every
+     * launch runs the checks of P3a / P3b, as before */
+    uint32_t order_checks_once;
 };
 
 /* ---- the row index of one log of a resident batch: what the row pass P1 has derived from op_id / action / mark_type and the log's header, columns that no entry
@@ -1650,6 +1663,14 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
      * launch that also stored rows_indexed — further up in the same kernel — and a reader sees either only after that whole kernel: it stands => the index stands. */
     constexpr bool kOps = kIdx && PTX_MARK_OPS_FORM;
     const bool ops_rd = kOps && idx_read && PTX_FRESH_ARGS(A).mark_ops && PTX_CONST_LOAD(&PTX_FRESH_ARGS(A).mark_ops_stand[log]) == N;
+    /* A standing log's row-order checks are not run again.  "The element exists when the op is applied" — row_of[target] < the delete's row, row_of[parent] < the
+     * insert's row — is a function of op_id / ref_a / action and the header, columns that no entry point may modify.  The launch that wrote the index ran every
+     * such check of P3a and P3b, and stored mark_ops_stand[log] = N behind P5a's loop, further down in the same kernel: no thread gets there with an error
+     * pending (PTX_BAIL_IF_ERROR ends P3a and P3b: every thread leaves).  A reader runs in a later kernel.  So ops_rd => the log passed them all, and a launch
+     * that resolves no references (out_refs) and has the host's leave leaves no delete in ilist / klist, skips the pass that reads them back, and P3b does not
+     * read row_of[parent].  The "no such element" raises (t < 0, p < 0) stay: they cost no LDS trip. */
+    constexpr bool kOnce = kOps && PTX_ORDER_CHECKS_ONCE_FORM;
+    const bool skip_chk = kOnce && ops_rd && PTX_FRESH_ARGS(A).order_checks_once != 0u && !out_refs;
     uint16_t* klist = L;
     uint16_t* bigp = ptx_alloc<uint16_t>(bp, n / (PTX_SMALL_BUCKET + 1u) + 2); /* parents with more than PTX_SMALL_BUCKET children */
     /* parents with two or more children (at most half of the elements' parents); once they are sorted the same words hold the bitmap that ranks a huge bucket */
@@ -2127,9 +2148,11 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
                         const int t = t_[u];
                         if (t < 0) ptx_raise(H, di[u], 1, PTX_ERR_ELEM_NOT_FOUND);
                         else ptx_atomic_or(&delbits[(uint32_t)t >> 5], 1u << ((uint32_t)t & 31u));
-                        const uint32_t sl = j < n ? PTX_JX(j, n) : j; /* j <= n; slot n is P1's spare */
-                        ilist[sl] = (uint16_t)(t < 0 ? 0xFFFF : t);
-                        klist[sl] = (uint16_t)di[u];
+                        if (!(kOnce && skip_chk)) {
+                            const uint32_t sl = j < n ? PTX_JX(j, n) : j; /* j <= n; slot n is P1's spare */
+                            ilist[sl] = (uint16_t)(t < 0 ? 0xFFFF : t);
+                            klist[sl] = (uint16_t)di[u];
+                        }
                     }
                 }
             };
@@ -2150,7 +2173,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         PTX_STAMP(12); /* end of P3a */
         PTX_REMAT_AT(2, PTX_REMAT_P3());
         /* the deletes' application-order check, now that row_of is complete: target element and row left in ilist / klist by P3a */
-        PTX_FORV(j0, d_fused, PTX_UV) {
+        if (!(kOnce && skip_chk)) PTX_FORV(j0, d_fused, PTX_UV) {
             uint32_t t[PTX_UV], i[PTX_UV], rt[PTX_UV];
 #pragma unroll
             for (int u = 0; u < PTX_UV; ++u) {
@@ -2164,6 +2187,7 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
 #pragma unroll
             for (int u = 0; u < PTX_UV; ++u)
                 if (t[u] != 0xFFFFu) {
+                    PTX_NOTE_ORDER_CHECK();
                     if (rt[u] >= i[u]) ptx_raise(H, i[u], 1, PTX_ERR_ELEM_NOT_FOUND);
                     if (out_refs && i[u] < N) out_refs[base + i[u]] = rt[u];
                 }
@@ -2173,7 +2197,8 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
                 const uint32_t j = d_fused + jj;
                 const uint32_t r = ptx_coherent_load32(&park[PTX_JX(j, D)]) & 0xFFFFu, i = r < N ? r : N - 1u;
                 const int t = ptx_elem_lookup24(ix, ref_a[i]);
-                if (t < 0 || row_of[t] >= i) ptx_raise(H, i, 1, PTX_ERR_ELEM_NOT_FOUND);
+                if (!(kOnce && skip_chk)) PTX_NOTE_ORDER_CHECK();
+                if (t < 0 || (!(kOnce && skip_chk) && row_of[t] >= i)) ptx_raise(H, i, 1, PTX_ERR_ELEM_NOT_FOUND);
                 else {
                     ptx_atomic_or(&delbits[(uint32_t)t >> 5], 1u << ((uint32_t)t & 31u));
                     if (out_refs) out_refs[base + i] = row_of[t];
@@ -2192,12 +2217,13 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
                 }
 #pragma unroll
             for (int u = 0; u < PTX_U; ++u)
-                if (PTX_IN(e0, u)) rp[u] = pe[u] < n ? (uint32_t)row_of[pe[u]] : 0u;
+                if (PTX_IN(e0, u)) rp[u] = !(kOnce && skip_chk) && pe[u] < n ? (uint32_t)row_of[pe[u]] : 0u;
 #pragma unroll
             for (int u = 0; u < PTX_U; ++u)
                 if (PTX_IN(e0, u)) {
                     /* the reference element must already exist when the op is applied (micromerge.ts:752) */
-                    if (pe[u] < n && rp[u] >= re[u]) ptx_raise(H, re[u], 1, PTX_ERR_ELEM_NOT_FOUND);
+                    if (!(kOnce && skip_chk)) PTX_NOTE_ORDER_CHECK();
+                    if (!(kOnce && skip_chk) && pe[u] < n && rp[u] >= re[u]) ptx_raise(H, re[u], 1, PTX_ERR_ELEM_NOT_FOUND);
                     /* now cnt[p] = END of p's bucket (no carry between the halves: a counter never exceeds n < 32767) */
                     seg[(ptx_atomic_add(&cntw[pe[u] >> 1], 1u << (16u * (pe[u] & 1u))) >> (16u * (pe[u] & 1u))) & 0xFFFFu] = (uint16_t)PTX_IX(e0, u);
                 }

@@ -715,6 +715,7 @@ struct ptx_ctx {
     int force_lds = 0;     /* ptx_set_launch_shape: LDS window per log (0 = the library's choice) */
     int stop_after = 0;    /* -DPTX_DIAG builds only (ptx_diag_stop_after): truncate the diagnostic kernel after a phase, for per-phase PMC deltas */
     uint32_t flags = 0;
+    bool no_lean256 = false; /* PTX_NO_LEAN256 in the environment when the context was made (read once: wants_lean is on every launch's path) */
     float check_replay_ms = 0.f, check_accum_ms = 0.f; /* the last ptx_check_patches (ptx_check_patches_ms) */
     unsigned long long* clocks = nullptr; /* device [PTX_NCLK], non-null only while ptx_merge_phase_cycles runs */
     /* staging of the SMALL result downloads (an editor session reads one replica per flush): a device block and a pinned host block that the context keeps and
@@ -1090,7 +1091,7 @@ static bool wants_w7(const ptx_ctx* ctx, const ptx_dbatch* b, uint32_t lds) {
 static uint32_t wants_lean(const ptx_ctx* ctx, const ptx_dbatch* b, bool with_rank, uint32_t lds) {
     const bool admit = b->chg_off && !(ctx->flags & PTX_FLAG_NO_ADMISSION);
     if (with_rank || !b->small_keys || ctx->clocks || ctx->stop_after || (admit && b->max_actors > 3)) return 0u;
-    if (b->threads == 256u && !getenv("PTX_NO_LEAN256")) return 256u; /* (whatever the window allows: no register cap in that build) */
+    if (b->threads == 256u && !ctx->no_lean256) return 256u; /* (whatever the window allows: no register cap in that build) */
     if (!wants_w7(ctx, b, lds)) return 0u;
     return b->threads == 64u || b->threads == 128u || b->threads == 192u ? b->threads : 0u;
 }
@@ -1160,6 +1161,7 @@ ptx_status ptx_create(int device_ordinal, uint32_t flags, ptx_ctx** out) {
     ptx_ctx* ctx = new ptx_ctx();
     ctx->device = device_ordinal;
     ctx->flags = flags;
+    ctx->no_lean256 = getenv("PTX_NO_LEAN256") != nullptr;
     ctx->cu_count = prop.multiProcessorCount;
     ctx->max_lds = 160 * 1024;
     if (hipSetDevice(device_ordinal) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1641,6 +1643,7 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
     A.row_index_write = idx_mode == 1 ? 1u : 0u;
     A.mark_ops = idx_mode ? b->mark_ops : nullptr; /* (with the index, under its protocol: its writer writes them, its readers read them) */
     A.mark_ops_stand = idx_mode ? b->mark_ops_stand : nullptr;
+    A.order_checks_once = idx_mode == 2 && b->mark_ops ? 1u : 0u; /* (a reading launch: a log whose word stands passed its row-order checks in the writing launch) */
     /* one workgroup per log; far more workgroups than the 256 CUs so the dispatcher load-balances.  Up to three launches (census_and_shape): the many at
      * their LDS window, the few that need a larger one, the logs beyond one CU's LDS through the HBM-staged kernel — the latter two on a side stream forked
      * from and joined to the caller's, so that they run beside the many instead of after them. */
@@ -1671,6 +1674,8 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
                 G.grid_bar = b->grid_bars + 2 * k;
                 G.n_logs = 1;
                 void* kargs[] = {(void*)&G};
+                /* (read per launch of a large log, not once in ptx_create: tests/test_gpu_biglog.py sets it after its context exists, and this loop is not the
+                 * hot path — it runs once per log of 16 384 rows and more) */
                 hipError_t ce = getenv("PTX_NO_COOPERATIVE") ? hipErrorCooperativeLaunchTooLarge /* (tests: a runtime without cooperative launch) */
                                                                : hipLaunchCooperativeKernel((const void*)ptx_merge_big_grid_kernel, dim3(b->big_grid_wgs[k]), dim3(PTX_BIG_GRID_THREADS), kargs, 0, st);
                 if (ce != hipSuccess) {
