@@ -86,6 +86,15 @@
 #ifndef PTX_NOTE_ORDER_CHECK
 #define PTX_NOTE_ORDER_CHECK() ((void)0)
 #endif
+#ifndef PTX_ORDER_WORDS_FORM
+/* which bodies write and read a standing log's order words (ptx_order_word below; an expression over the body's template parameters, only where P5a's second form
+ * is): the three-wave lean build, where it was measured.  Every other body compiles to what it was */
+#define PTX_ORDER_WORDS_FORM (kLean && kThreads == 192u)
+#endif
+/* a log enters P3, the causal tree: counted by the CPU test-suite's driver of the order words, nothing anywhere else */
+#ifndef PTX_NOTE_TREE_PASS
+#define PTX_NOTE_TREE_PASS() ((void)0)
+#endif
 #ifndef PTX_UB64
 #define PTX_UB64 1u
 #endif
@@ -185,6 +194,11 @@ struct PtxMergeArgs {
     /* the host's leave to take a standing log's row-order checks as passed (see where ops_rd is derived): set in launches that read the operand words, 0 = every
      * launch runs the checks of P3a / P3b, as before */
     uint32_t order_checks_once;
+    /* the order words of the batch (see ptx_order_word below), handed out with the operand words or not at all: all three nullptr = every launch runs P3, as
+     * before.  The launch that writes the index writes them; a launch that reads the index reads those of the logs whose word stands */
+    uint32_t* order_words;  /* optional: one word per list element, log l from word ptx_row_index_off(row offset, l) */
+    uint32_t* order_bits;   /* with it: the tombstone bitmaps by element index, log l from word ptx_row_bits_off(row offset, l) */
+    uint32_t* order_stands; /* with it [n_logs]: N once the order words and the tombstone words of the log stand, else 0 */
 };
 
 /* ---- the row index of one log of a resident batch: what the row pass P1 has derived from op_id / action / mark_type and the log's header, columns that no entry
@@ -411,6 +425,13 @@ PTX_HD uint64_t ptx_mark_operand_pack(uint32_t key_a, uint32_t key_b, uint32_t s
     const uint32_t hi = (comment_id & 0xFFFFu) | (ptx_side_class(side_a) << 16) | (ptx_side_class(side_b) << 18) | (bad_comment ? 1u << 20 : 0u);
     return (uint64_t)((key_a & 0xFFFFu) | (key_b << 16)) | ((uint64_t)hi << 32);
 }
+/* ---- the order word of a list element of an indexed log: what P3, the causal tree, derives from op_id / ref_a / action and the log's header, columns that no
+ *      entry point may modify (16-bit id keys: only such logs have an index; n <= 32 766 and N <= 65 534, so both halves fit).  Element e — the rank of its id
+ *      key among the inserts' keys, the same in every launch whatever order the row pass listed the inserts in — has word e of the log's region:
+ *      row_of[e] | rnk[e] << 16, the row that inserted it and its document position, tombstones included (the RGA position is unique).  The tombstone bit of
+ *      element e is bit e of the log's (n >> 5) + 1 tombstone words.  Everything behind P3 reads these two arrays, the tombstones and the id bitmap, nothing else
+ *      of the tree. ---- */
+PTX_HD uint32_t ptx_order_word(uint32_t row, uint32_t pos) { return (row & 0xFFFFu) | (pos << 16); }
 /* P5a gathers the operands of one mark op through its row: counted by the CPU test-suite's driver of the operand words, nothing anywhere else */
 #ifndef PTX_NOTE_MARK_GATHER
 #define PTX_NOTE_MARK_GATHER() ((void)0)
@@ -1671,6 +1692,14 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
      * read row_of[parent].  The "no such element" raises (t < 0, p < 0) stay: they cost no LDS trip. */
     constexpr bool kOnce = kOps && PTX_ORDER_CHECKS_ONCE_FORM;
     const bool skip_chk = kOnce && ops_rd && PTX_FRESH_ARGS(A).order_checks_once != 0u && !out_refs;
+    /* A standing log's element order is read, not rebuilt.  row_of[e], rnk[e] and the tombstone of element e are functions of op_id / ref_a / action and the
+     * header — e is the rank of the id key, not a slot of this launch's lists —, columns that no entry point may modify.  The launch that wrote the index stored
+     * all n order words and the tombstone words behind the barrier that ends P3, then order_stands[log] = N: no thread gets there with an error pending from P3a
+     * or P3b (PTX_BAIL_IF_ERROR: every thread leaves), and P3c / P3d raise nothing.  A reader runs in a later kernel (launch_merge), so it sees the word only
+     * after that whole kernel has ended: the word stands => the log passed every check of P3 and all its words are complete.  Such a launch, if it resolves no
+     * references (out_refs: the deletes' rows come out of P3a), fills the three LDS arrays from the words and runs nothing of P3.  ord_rd => ops_rd => idx_read. */
+    constexpr bool kOrd = kOps && PTX_ORDER_WORDS_FORM;
+    const bool ord_rd = kOrd && ops_rd && !out_refs && PTX_FRESH_ARGS(A).order_words && PTX_CONST_LOAD(&PTX_FRESH_ARGS(A).order_stands[log]) == N;
     uint16_t* klist = L;
     uint16_t* bigp = ptx_alloc<uint16_t>(bp, n / (PTX_SMALL_BUCKET + 1u) + 2); /* parents with more than PTX_SMALL_BUCKET children */
     /* parents with two or more children (at most half of the elements' parents); once they are sorted the same words hold the bitmap that ranks a huge bucket */
@@ -1779,14 +1808,21 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
      *      Every row and key that comes out of the index is clamped as if it came from the rows. ---- */
     if (kIdx && idx_read) {
         const uint32_t* const ins = park - ((n + 3u) & ~3u); /* the inserts' words: 16-byte aligned */
-        PTX_P3A_DQ(0u, p3_dq)
+        /* (ord_rd) the log's order words, beside the insert words at the same region offset, and its tombstone words: complete since before this kernel began */
+        const uint32_t* const ordw = kOrd && ord_rd ? PTX_FRESH_ARGS(A).order_words + ptx_row_index_off(base, log) : ins;
+        if (!(kOrd && ord_rd)) { PTX_P3A_DQ(0u, p3_dq) }
         PTX_FOR(w, nw + 1) {
             PtxBitWord z;
             z.bits = 0;
             z.pre = 0;
             ix.ib[w] = z;
         }
-        PTX_FOR(w, nwe + 1) delbits[w] = 0;
+        if (kOrd && ord_rd) { /* the tombstones come in as the writer's P3 left them (bits behind the n-th: none, as if computed) */
+            const uint32_t* const tb = PTX_FRESH_ARGS(A).order_bits + ptx_row_bits_off(base, log);
+            PTX_FOR(w, nwe + 1) delbits[w] = w < nwe ? tb[w] & (w == (n >> 5) ? (1u << (n & 31u)) - 1u : 0xFFFFFFFFu) : 0u;
+        } else {
+            PTX_FOR(w, nwe + 1) delbits[w] = 0;
+        }
         {
             const uint32_t* const mb = PTX_FRESH_ARGS(A).row_index_bits + ptx_row_bits_off(base, log);
             PTX_FOR(w, (K >> 5) + 1) maddbits[w] = mb[w];
@@ -1805,9 +1841,19 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             if (in && j < n) {
                 const uint32_t r_ = w & 0xFFFFu;
                 const uint32_t key = ptx_min(w >> 16, keyspace - 1u);
-                ilist[j] = (uint16_t)(r_ < N ? r_ : N - 1u);
-                klist[j] = (uint16_t)key;
+                if (!(kOrd && ord_rd)) { /* (a log whose order words stand lists nothing: the id bits alone, for P5a's key look-ups) */
+                    ilist[j] = (uint16_t)(r_ < N ? r_ : N - 1u);
+                    klist[j] = (uint16_t)key;
+                }
                 ptx_atomic_or(&ix.ib[key >> 5].bits, 1u << (key & 31u));
+            }
+        };
+        /* element j's row and document position out of its order word: the row clamped to the log, the position to what `alive` covers, as if computed */
+        auto puto = [&](bool in, uint32_t j, uint32_t w) {
+            if (in && j < n) {
+                const uint32_t r_ = w & 0xFFFFu;
+                row_of[j] = (uint16_t)(r_ < N ? r_ : N - 1u);
+                par[j] = (uint16_t)ptx_min(w >> 16, n);
             }
         };
         PTX_FORV(g0, (n + 3u) >> 2, 2) {
@@ -1816,6 +1862,19 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             const uint32_t ga = in_a ? PTX_IX(g0, 0) : 0u, gb = in_b ? PTX_IX(g0, 1) : 0u;
             PTX_IDX_LOAD4(a0, a1, a2, a3, ins, ga, n)
             PTX_IDX_LOAD4(b0, b1, b2, b3, ins, gb, n)
+            if (kOrd && ord_rd) { /* four order words per load, beside the insert words: all four loads of a step in flight together */
+                uint32_t c0, c1, c2, c3, d0, d1, d2, d3;
+                PTX_IDX_LOAD4(c0, c1, c2, c3, ordw, ga, n)
+                PTX_IDX_LOAD4(d0, d1, d2, d3, ordw, gb, n)
+                puto(in_a, 4u * ga, c0);
+                puto(in_a, 4u * ga + 1u, c1);
+                puto(in_a, 4u * ga + 2u, c2);
+                puto(in_a, 4u * ga + 3u, c3);
+                puto(in_b, 4u * gb, d0);
+                puto(in_b, 4u * gb + 1u, d1);
+                puto(in_b, 4u * gb + 2u, d2);
+                puto(in_b, 4u * gb + 3u, d3);
+            }
             put(in_a, 4u * ga, a0);
             put(in_a, 4u * ga + 1u, a1);
             put(in_a, 4u * ga + 2u, a2);
@@ -1826,8 +1885,10 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             put(in_b, 4u * gb + 3u, b3);
         }
         PTX_SYNC_LDS();
-        PTX_P3A_LOAD(0u, p3_i, p3_id, p3_ra, p3_di, p3_dra, p3_dq)
-        PTX_P3A_DQ(1u, p3_dq)
+        if (!(kOrd && ord_rd)) {
+            PTX_P3A_LOAD(0u, p3_i, p3_id, p3_ra, p3_di, p3_dra, p3_dq)
+            PTX_P3A_DQ(1u, p3_dq)
+        }
         ptx_bitwords_prefix<kThreads>(ix.ib, nw + 1, &H->scan_tmp[16]);
     } else
     /* ---- P1: ONE pass over the rows: id bitmaps, row lists per class ---- */
@@ -2081,8 +2142,13 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
         ow_[u] = (opw_)[k_];                                                \
     }
 #define PTX_MARK_OPW(F_) ((const uint64_t*)F_.mark_ops + ptx_row_index_off(base, log))
-    /* ---- P3: causal tree of the inserts -> document position of every element ---- */
-    {
+    /* ---- P3: causal tree of the inserts -> document position of every element (a log whose order words stand has all three results in LDS already: the
+     *      barriers of the error check above stand between their stores and the first read of P4) ---- */
+    /* (ord_rd again, from the kernel arguments and the log's word as they are read here, beside the header's scalars: the same answer — a reading launch stores
+     * neither — and nothing of it carried through the row pass) */
+    const bool tree_stands = kOrd && ops_rd && !out_refs && PTX_FRESH_ARGS(A).order_words && PTX_CONST_LOAD(&PTX_FRESH_ARGS(A).order_stands[log]) == N;
+    if (!(kOrd && tree_stands)) {
+        PTX_NOTE_TREE_PASS();
         /* children per parent -> bucket starts -> bucket ends; 16-bit counters, two per atomically updated word */
         uint16_t* cnt = (uint16_t*)cntw;
         uint16_t* srt = ilist;       /* children of every parent, descending opId, parents ascending (ilist is dead after P3b) */
@@ -2471,6 +2537,21 @@ PTX_DEV uint32_t ptx_merge_log_body(const PtxMergeArgs& A, uint32_t log, uint8_t
             }
         }
         PTX_SYNC_LDS();
+        /* the launch that writes the log's index: P3 has passed (nobody is here with an error pending) and row_of, the positions and the tombstones are complete
+         * behind the barrier above.  The order words go out four at a time — two 8-byte LDS reads, one coalesced 16-byte store that nothing in this kernel
+         * waits for —, the tombstone words behind them, and ONE lane says so; who reads this does so in a LATER kernel (launch_merge).  (The pointers come from
+         * the kernel arguments here, where they are used: nothing of this is carried through the tree.) */
+        if (kOrd && small_keys && PTX_FRESH_ARGS(A).row_index && PTX_FRESH_ARGS(A).row_index_write && PTX_FRESH_ARGS(A).order_words) {
+            uint32_t* const ow = PTX_FRESH_ARGS(A).order_words + ptx_row_index_off(base, log);
+            PTX_FOR(g, (n + 3u) >> 2) {
+                uint32_t w4[4];
+                PTX_IDX_PACK4(w4, row_of, rnk, g, n)
+                PTX_IDX_STORE4(ow, g, w4)
+            }
+            uint32_t* const tb = PTX_FRESH_ARGS(A).order_bits + ptx_row_bits_off(base, log);
+            PTX_FOR(w, nwe) tb[w] = delbits[w];
+            PTX_LEADER { PTX_FRESH_ARGS(A).order_stands[log] = N; }
+        }
     }
     PTX_STAMP(18); /* document positions stand; the mark list comes back from its park */
     PTX_REMAT_AT(7, PTX_REMAT());

@@ -847,6 +847,10 @@ struct ptx_dbatch {
      * at all, written by the index's one writer, read by its readers; neither block nullptr or both */
     uint64_t* mark_ops = nullptr;
     uint32_t* mark_ops_stand = nullptr;
+    /* the order words (merge_core.h ptx_order_word): what P3 derives from op_id / ref_a / action and the headers — per element its row and its document position,
+     * 4 bytes per row of capacity at the index's own region offsets, the tombstone bitmaps addressed like row_index_bits, and one word per log that says whether
+     * the log's words stand.  Made with the operand words or not at all (all three nullptr or none), written by the index's one writer, read by its readers */
+    uint32_t *order_words = nullptr, *order_bits = nullptr, *order_stands = nullptr;
     mutable int index_state = 0;               /* 0 nobody has written it; 1 a launch is being enqueued that writes it; 2 written by a launch of context index_writer on index_stream, index_ev recorded behind it; 3 that launch has ended */
     mutable uint64_t index_writer = 0;         /* ptx_ctx::serial of the writing context */
     mutable hipStream_t index_stream = nullptr;
@@ -886,7 +890,14 @@ struct ptx_dresult {
 };
 
 static std::mutex g_index_mu;                        /* the index_state / index_stream / index_ev of every batch */
+static void free_order_words(ptx_dbatch* b) {
+    (void)ptx_dev_free(b->order_words);
+    (void)ptx_dev_free(b->order_bits);
+    (void)ptx_dev_free(b->order_stands);
+    b->order_words = b->order_bits = b->order_stands = nullptr;
+}
 static void free_mark_ops(ptx_dbatch* b) {
+    free_order_words(b);
     (void)ptx_dev_free(b->mark_ops);
     (void)ptx_dev_free(b->mark_ops_stand);
     b->mark_ops = nullptr;
@@ -1068,6 +1079,17 @@ static ptx_status census_and_shape(ptx_ctx* ctx, ptx_dbatch* b, bool have_hdr, b
             if (eo != hipSuccess) {
                 (void)hipGetLastError();
                 free_mark_ops(b);
+            } else {
+                /* the order words: 4 bytes per row and a bit per row more; a failed allocation leaves the batch with its operand words and without them,
+                 * never with an error.  Only the word per log is zeroed */
+                hipError_t er = ptx_dev_malloc((void**)&b->order_stands, (size_t)b->n_logs * 4);
+                if (er == hipSuccess) er = ptx_dev_malloc((void**)&b->order_words, (size_t)ptx_row_index_words(b->n_ops, b->n_logs) * 4);
+                if (er == hipSuccess) er = ptx_dev_malloc((void**)&b->order_bits, (size_t)ptx_row_bits_words(b->n_ops, b->n_logs) * 4);
+                if (er == hipSuccess) er = hipMemsetAsync(b->order_stands, 0, (size_t)b->n_logs * 4, ctx->stream);
+                if (er != hipSuccess) {
+                    (void)hipGetLastError();
+                    free_order_words(b);
+                }
             }
         }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->index_ev, hipEventDisableTiming); /* recorded behind the one merge that writes the index (launch_merge) */
@@ -1644,6 +1666,9 @@ static ptx_status launch_merge(ptx_ctx* ctx, const ptx_dbatch* b, ptx_dresult* r
     A.mark_ops = idx_mode ? b->mark_ops : nullptr; /* (with the index, under its protocol: its writer writes them, its readers read them) */
     A.mark_ops_stand = idx_mode ? b->mark_ops_stand : nullptr;
     A.order_checks_once = idx_mode == 2 && b->mark_ops ? 1u : 0u; /* (a reading launch: a log whose word stands passed its row-order checks in the writing launch) */
+    A.order_words = idx_mode ? b->order_words : nullptr; /* (with the operand words, under the index's protocol) */
+    A.order_bits = idx_mode ? b->order_bits : nullptr;
+    A.order_stands = idx_mode ? b->order_stands : nullptr;
     /* one workgroup per log; far more workgroups than the 256 CUs so the dispatcher load-balances.  Up to three launches (census_and_shape): the many at
      * their LDS window, the few that need a larger one, the logs beyond one CU's LDS through the HBM-staged kernel — the latter two on a side stream forked
      * from and joined to the caller's, so that they run beside the many instead of after them. */
@@ -1758,6 +1783,19 @@ int ptx_debug_mark_operands(ptx_ctx* ctx, const ptx_dbatch* b, uint32_t* n_stand
     if (ptx_enter(ctx) != hipSuccess) return -1;
     std::vector<uint32_t> h(b->n_logs);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(h.data(), b->mark_ops_stand, (size_t)b->n_logs * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (n_stand)
+        for (uint32_t v : h) *n_stand += v != 0u;
+    return 0;
+}
+
+/* Test hook beside ptx_debug_mark_operands, NOT part of the C ABI: *n_stand = the logs whose order words stand (order_stands set), read after everything this
+ * context has enqueued.  Returns -1 for a batch without order words, else 0. */
+int ptx_debug_order_words(ptx_ctx* ctx, const ptx_dbatch* b, uint32_t* n_stand) {
+    if (n_stand) *n_stand = 0;
+    if (!ctx || !b || !b->order_words || !b->order_stands) return -1;
+    if (ptx_enter(ctx) != hipSuccess) return -1;
+    std::vector<uint32_t> h(b->n_logs);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(h.data(), b->order_stands, (size_t)b->n_logs * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     if (n_stand)
         for (uint32_t v : h) *n_stand += v != 0u;
     return 0;
