@@ -821,6 +821,49 @@ ptx_status ptx_view_find_snippets(ptx_ctx* ctx, const ptx_dview* v, const uint16
                                   uint32_t before, uint32_t after, ptx_snippets* out);
 void ptx_snippets_free(ptx_snippets* m);
 
+/* ---- find and replace on a resident text view: hits into change() input ----
+ * The reference's editor turns a ProseMirror ReplaceStep into a `delete` followed by an `insert` at the same index (bridge.ts:425-446).  This answers, for every
+ * log of a view: which matches String.prototype.replaceAll(pattern, ...) would replace, and the InputOperations that do it — the `in` of ptx_change.
+ *   matches            exactly those of ptx_view_find_text with max_hits_per_log = 0xFFFFFFFF, flags included (PTX_FIND_ASCII_NOCASE), over the same text
+ *   chosen matches     greedy, leftmost, non-overlapping, over ALL matches of the log: the first match is chosen, and after a chosen match at unit u the next
+ *                      chosen one is the first with hit_unit >= u + n_pattern — what replaceAll and Python's str.replace do.  The choice does not look at
+ *                      element boundaries
+ *   replaceable        a chosen match is replaceable iff it covers whole elements: pre[hit_start] == hit_unit and pre[hit_end] == hit_unit + n_pattern (the view
+ *                      holds pre[0 .. n_visible]).  A chosen match that starts or ends inside a multi-unit element is skipped and counted (n_chosen -
+ *                      n_replaced); it still blocks the matches it overlaps.  Empty-string elements inside [hit_start, hit_end) go with the match; those
+ *                      directly before or after it stay
+ *   ops                a log with R > 0 replaceable matches gets ONE Change.  Its matches are taken in DESCENDING hit order, so no index needs adjusting; each
+ *                      gives PTX_IN_DELETE {index: hit_start, count: hit_end - hit_start} and then, if n_replacement > 0, PTX_IN_INSERT {index: hit_start,
+ *                      count: n_replacement, payload: 0} — the order of bridge.ts:425-446.  `values` is the caller's n_replacement value ids once, shared by
+ *                      every insert: one element per id.  The replacement is never rescanned
+ *   shape              ptx_change demands in->n_logs == base->n_logs, so the call takes n_batch_logs: ops.n_logs == n_batch_logs, chg_off has n_batch_logs + 1
+ *                      entries, view log l is batch log first_log + l, and logs outside the view's range make no Change.  ops.actor and ops.max_actors are
+ *                      left NULL / 0 for the caller to fill in
+ *   per-log status     the view's (ptx_matches.status), and PTX_ERR_CAPACITY where the Change would make more than the PTX_CHANGE_ROWS_MAX rows ptx_change accepts
+ *                      per log: rows = the sum of hit_end - hit_start + R * n_replacement.  A log that is not PTX_OK gets no ops; the counts of a
+ *                      PTX_ERR_CAPACITY log are still reported
+ * PTX_ERR_INVALID_ARG: the argument errors of ptx_view_find_text; n_replacement > PTX_CHANGE_ROWS_MAX; n_replacement > 0 with a NULL `replacement`;
+ * n_batch_logs < first_log + n_logs of the view.  More than 2^32 - 1 matches in the view is PTX_ERR_CAPACITY, as for find.  An empty view returns an all-zero
+ * plan (chg_off all 0, op_off = {0}).  `pattern` and `replacement` are HOST pointers, copied before the call returns.  elem_rank is not needed
+ * (PTX_FLAG_NO_ELEM_RANK contexts work: the plan reads no elem_rank — ptx_change does).  Synchronises. */
+#define PTX_CHANGE_ROWS_MAX 65534u     /* rows the Changes of ONE log may make in one ptx_change call */
+typedef struct ptx_replace_plan {
+    uint32_t n_logs;               /* of the view */
+    uint32_t n_pattern;
+    float kernel_ms;               /* HIP events around every launch of the call */
+    uint32_t n_replacement;
+    const uint32_t* status;        /* [n_logs] */
+    const uint32_t* n_matches;     /* [n_logs] ALL matches of the log */
+    const uint32_t* n_chosen;      /* [n_logs] the greedy, non-overlapping ones */
+    const uint32_t* n_replaced;    /* [n_logs] those of them that cover whole elements */
+    ptx_input_ops ops;             /* its pointers point into the plan's blocks */
+    void* owner;
+} ptx_replace_plan;
+/* Owned by the library until ptx_replace_plan_free. */
+ptx_status ptx_view_replace_plan(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement,
+                                 uint32_t n_replacement, uint32_t n_batch_logs, ptx_replace_plan* out);
+void ptx_replace_plan_free(ptx_replace_plan* m);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

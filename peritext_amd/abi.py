@@ -360,6 +360,26 @@ class ptx_snippets(C.Structure):
     ]
 
 
+# find and replace on a view (ptx_view_replace_plan; peritext_amd/csrc/replace_core.h)
+REPLACE_TILE = 64  # PTX_REPLACE_TILE: hits per step of the select walk
+CHANGE_ROWS_MAX = 65534  # PTX_CHANGE_ROWS_MAX: rows the Changes of one log may make in one ptx_change call
+
+
+class ptx_replace_plan(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("n_pattern", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("n_replacement", C.c_uint32),
+        ("status", u32p),
+        ("n_matches", u32p),
+        ("n_chosen", u32p),
+        ("n_replaced", u32p),
+        ("ops", ptx_input_ops),
+        ("owner", C.c_void_p),
+    ]
+
+
 # numpy dtypes with the same layout
 import numpy as np  # noqa: E402
 
@@ -462,6 +482,8 @@ FUNCTIONS = {
     "ptx_view_text_slices": (C.c_int32, [vp, vp, u64p, u32p, u32p, C.POINTER(ptx_slices)]),
     "ptx_view_find_snippets": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_snippets)]),
     "ptx_snippets_free": (None, [C.POINTER(ptx_snippets)]),
+    "ptx_view_replace_plan": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.POINTER(ptx_replace_plan)]),
+    "ptx_replace_plan_free": (None, [C.POINTER(ptx_replace_plan)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

@@ -41,6 +41,7 @@
 #include "find_core.h"
 #include "slice_core.h"
 #include "view_core.h"
+#include "replace_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -680,6 +681,17 @@ extern "C" __global__ void __launch_bounds__(256) ptx_view_locate_kernel(PtxView
 extern "C" __global__ void __launch_bounds__(256) ptx_view_windows_kernel(PtxViewArgs A) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k < A.n_hits) ptx_view_windows_one(A, k);
+}
+
+/* ---- find and replace on a view (replace_core.h): after the view's own hit passes, one wave per log chooses the greedy non-overlapping hits by pointer doubling
+ *      and marks those that cover whole elements; ptx_find_offsets_kernel scans the Changes and the ops; a lane per hit writes the InputOperations ---- */
+extern "C" __global__ void __launch_bounds__(64) ptx_replace_select_kernel(PtxReplaceArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_replace_lds[PTX_REPLACE_LDS_BYTES];
+    if (blockIdx.x < A.V.F.T.n_logs) ptx_replace_select_log<64>(A, blockIdx.x, ptx_replace_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_replace_emit_kernel(PtxReplaceArgs A) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < A.V.n_hits) ptx_replace_emit_one(A, k); /* (the grid is ceil(n_hits / 256) <= 2^24 blocks: k does not wrap) */
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -3048,6 +3060,190 @@ ptx_status ptx_view_find_snippets(ptx_ctx* ctx, const ptx_dview* v, const uint16
     return PTX_OK;
 }
 
+/* ---- find and replace on a view (replace_core.h): count -> offsets -> positions -> locate -> select -> the two scans -> the sizes come down -> emit -> one
+ *      download.  Three waits: the number of hits, the number of Changes and ops, the plan.  The hits themselves never leave the device ---- */
+void ptx_replace_plan_free(ptx_replace_plan* m) {
+    if (!m) return;
+    delete (ptx_host_result*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+/* the arguments are checked; h->pinned[0]: status | n_matches | n_chosen | n_replaced | hit_off (scratch) | chg_off,  h->pinned[1]: op_off | index | count | payload |
+ * action | mark_type | values */
+static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement, uint32_t n_replacement,
+                                    uint32_t n_batch_logs, ptx_host_result* h, ptx_replace_plan* out) {
+    PTX_HIP(ctx, ptx_enter(ctx));
+    const uint32_t n_logs = v->n_logs;
+    const uint64_t no = (uint64_t)n_logs + 1, nbo = (uint64_t)n_batch_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status | n_matches | n_chosen | n_replaced | hit_off | chg_off — what comes down — | n_ops | makes | op_log_off | the pattern */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), ho_at = 4 * st_bytes, co_at = ho_at + a16(no * 8), down0 = co_at + a16(nbo * 8);
+    const uint64_t no_at = down0, mk_at = no_at + st_bytes, ol_at = mk_at + a16((uint64_t)n_batch_logs * 4), pat_at = ol_at + a16(no * 8), blk0 = pat_at + a16((uint64_t)n_pattern * 2);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, blk0);
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t nhits = 0, sizes[2] = {0, 0}; /* Changes, InputOperations */
+    bool too_many = false;
+    PtxReplaceArgs R;
+    memset(&R, 0, sizeof(R));
+    if (e == hipSuccess) {
+        memset(hp0, 0, blk0); /* an empty view, a view without hits: the all-zero plan */
+        view_text_args(v, R.V.F.T);
+        R.V.F.n_matches = (uint32_t*)(d0 + st_bytes);
+        R.V.F.hit_off = (uint64_t*)(d0 + ho_at);
+        R.V.F.pattern = (const uint16_t*)(d0 + pat_at);
+        R.V.F.n_pattern = n_pattern;
+        R.V.F.flags = flags;
+        R.V.F.cap = 0xFFFFFFFFu;
+        R.V.pre_off = v->pre_off;
+        R.V.pre = v->pre;
+        R.n_replacement = n_replacement;
+        R.first_log = v->first_log;
+        R.n_batch_logs = n_batch_logs;
+        R.status = (uint32_t*)d0;
+        R.n_chosen = (uint32_t*)(d0 + 2 * st_bytes);
+        R.n_replaced = (uint32_t*)(d0 + 3 * st_bytes);
+        R.chg_off = (uint64_t*)(d0 + co_at);
+        R.n_ops = (uint32_t*)(d0 + no_at);
+        R.makes = (uint32_t*)(d0 + mk_at);
+        R.op_log_off = (uint64_t*)(d0 + ol_at);
+        if (n_logs) memcpy(hp0, v->h_status.data(), (size_t)n_logs * 4);
+        memcpy(hp0 + pat_at, pattern, (size_t)n_pattern * 2); /* the caller's pattern is free to go */
+    }
+    const uint64_t* hit_off = (const uint64_t*)(hp0 + ho_at);
+    if (e == hipSuccess && n_logs) {
+        e = hipMemcpyAsync(d0 + pat_at, hp0 + pat_at, (size_t)n_pattern * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_find_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, R.V.F);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)R.V.F.n_matches, 0xFFFFFFFFu, R.V.F.hit_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + st_bytes, d0 + st_bytes, st_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + ho_at, d0 + ho_at, no * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nhits = hit_off[n_logs];
+        if (e == hipSuccess && nhits > 0xFFFFFFFFull) too_many = true, e = hipErrorInvalidValue; /* a lane per hit */
+    }
+    /* block 1, the device's only: hit_unit | hit_start | hit_end | sel */
+    const uint64_t col = a16(nhits * 4);
+    if (e == hipSuccess && nhits) {
+        e = ptx_dev_malloc((void**)&d1, 4 * col + 16);
+        if (e == hipSuccess) {
+            R.V.n_hits = (uint32_t)nhits;
+            R.V.F.hit_unit = (uint32_t*)d1;
+            R.V.F.hit_start = (uint32_t*)(d1 + col);
+            R.V.F.hit_end = (uint32_t*)(d1 + 2 * col);
+            R.sel = (uint32_t*)(d1 + 3 * col);
+            e = hipMemsetAsync(R.makes, 0, (size_t)n_batch_logs * 4, ctx->stream); /* the logs outside the view's range make no Change */
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_view_positions_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, R.V.F);
+            hipLaunchKernelGGL(ptx_view_locate_kernel, dim3((uint32_t)((nhits + 255) / 256)), dim3(256), 0, ctx->stream, R.V);
+            hipLaunchKernelGGL(ptx_replace_select_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, R);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)R.makes, 0xFFFFFFFFu, R.chg_off, n_batch_logs);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)R.n_ops, 0xFFFFFFFFu, R.op_log_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&sizes[0], R.chg_off + n_batch_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&sizes[1], R.op_log_off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess && (sizes[0] > n_logs || sizes[1] > 2 * nhits)) e = hipErrorInvalidValue; /* (a Change per log, two ops per hit at the most) */
+    }
+    /* block 2, device and pinned host alike: op_off | index | count | payload | action | mark_type; the host's goes on with the value ids */
+    const uint64_t nc = sizes[0], ni = sizes[1], oo_bytes = a16((nc + 1) * 8), c4 = a16(ni * 4), c1 = a16(ni), val_at = oo_bytes + 3 * c4 + 2 * c1,
+                   blk2 = val_at + a16((uint64_t)n_replacement * 4) + 16;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    if (e == hipSuccess) {
+        memset(hp1, 0, oo_bytes); /* no Change: op_off = {0} */
+        if (n_replacement) memcpy(hp1 + val_at, replacement, (size_t)n_replacement * 4); /* the caller's ids are free to go */
+    }
+    if (e == hipSuccess && ni) {
+        e = ptx_dev_malloc((void**)&d2, val_at + 16);
+        if (e == hipSuccess) {
+            R.op_off = (uint64_t*)d2;
+            R.index = (uint32_t*)(d2 + oo_bytes);
+            R.count = (uint32_t*)(d2 + oo_bytes + c4);
+            R.payload = (uint32_t*)(d2 + oo_bytes + 2 * c4);
+            R.action = d2 + oo_bytes + 3 * c4;
+            R.mark_type = d2 + oo_bytes + 3 * c4 + c1;
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_replace_emit_kernel, dim3((uint32_t)((nhits + 255) / 256)), dim3(256), 0, ctx->stream, R);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp1, d2, val_at, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess && nhits) { /* the plan's status and counts, and chg_off: with the ops, one wait */
+        e = hipMemcpyAsync(hp0, d0, st_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + 2 * st_bytes, d0 + 2 * st_bytes, 2 * st_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + co_at, d0 + co_at, nbo * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && ni) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
+    }
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    (void)ptx_dev_free(d2);
+    if (e != hipSuccess) {
+        if (too_many) return fail(ctx, PTX_ERR_CAPACITY, "more than 2^32 - 1 matches in the view: plan a smaller range");
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view replace plan: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->n_pattern = n_pattern;
+    out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->n_replacement = n_replacement;
+    out->status = (const uint32_t*)hp0;
+    out->n_matches = (const uint32_t*)(hp0 + st_bytes);
+    out->n_chosen = (const uint32_t*)(hp0 + 2 * st_bytes);
+    out->n_replaced = (const uint32_t*)(hp0 + 3 * st_bytes);
+    out->ops.n_logs = n_batch_logs;
+    out->ops.max_actors = 0;
+    out->ops.chg_off = (const uint64_t*)(hp0 + co_at);
+    out->ops.op_off = (const uint64_t*)hp1;
+    out->ops.index = (const uint32_t*)(hp1 + oo_bytes);
+    out->ops.count = (const uint32_t*)(hp1 + oo_bytes + c4);
+    out->ops.payload = (const uint32_t*)(hp1 + oo_bytes + 2 * c4);
+    out->ops.action = hp1 + oo_bytes + 3 * c4;
+    out->ops.mark_type = hp1 + oo_bytes + 3 * c4 + c1;
+    out->ops.values = (const uint32_t*)(hp1 + val_at);
+    out->ops.n_values = n_replacement;
+    out->ops.actor = nullptr;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_replace_plan(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement, uint32_t n_replacement,
+                                 uint32_t n_batch_logs, ptx_replace_plan* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_find_check(ctx, pattern, n_pattern, flags);
+    if (st != PTX_OK) return st;
+    if (n_replacement > PTX_CHANGE_ROWS_MAX) return fail(ctx, PTX_ERR_INVALID_ARG, "replacement of more than PTX_CHANGE_ROWS_MAX elements");
+    if (n_replacement && !replacement) return fail(ctx, PTX_ERR_INVALID_ARG, "replacement is NULL");
+    if ((uint64_t)n_batch_logs < (uint64_t)v->first_log + v->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "n_batch_logs ends before the view's range");
+    ptx_host_result* h = new ptx_host_result();
+    st = view_replace_impl(ctx, v, pattern, n_pattern, flags, replacement, n_replacement, n_batch_logs, h, out);
+    if (st != PTX_OK) {
+        delete h;
+        memset(out, 0, sizeof(*out));
+        return st;
+    }
+    out->owner = h;
+    return PTX_OK;
+}
+
 ptx_status ptx_view_text_slices(ptx_ctx* ctx, const ptx_dview* v, const uint64_t* slice_off, const uint32_t* slice_start, const uint32_t* slice_end, ptx_slices* out) {
     if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
     memset(out, 0, sizeof(*out));
@@ -4096,7 +4292,7 @@ ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* m
                 grow[l] += in->count[q];
             } else if (a == PTX_IN_DELETE) rows += in->count[q];
             else rows += 1;
-            if (rows > 65534u) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: more than 65534 ops for one log");
+            if (rows > PTX_CHANGE_ROWS_MAX) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: more than 65534 ops for one log");
         }
         out_off[l + 1] = out_off[l] + rows;
     }

@@ -151,6 +151,28 @@ class TextView:
         finally:
             eng.lib.ptx_snippets_free(C.byref(m))
 
+    def replace_plan(self, pattern, replacement_ids, n_batch_logs, ascii_nocase=False):
+        """replaceAll as change() input (ptx_view_replace_plan): per log the matches str.replace would replace — greedy, leftmost, non-overlapping — and, for those
+        that cover whole elements, a delete and an insert of the value ids `replacement_ids` (one element each) per match, in descending order, as ONE Change
+        per log: wire.ReplacePlan, its `ops` shaped for a batch of n_batch_logs logs."""
+        eng, pat = self.engine, self._pattern(pattern)
+        ids = np.ascontiguousarray(replacement_ids, dtype=np.uint32)
+        m = abi.ptx_replace_plan()
+        eng._check(eng.lib.ptx_view_replace_plan(eng.ctx, self.handle, pat.ctypes.data_as(abi.u16p), len(pat), abi.FIND_ASCII_NOCASE if ascii_nocase else 0,
+                                                 ids.ctypes.data_as(abi.u32p) if len(ids) else C.cast(None, abi.u32p), len(ids), n_batch_logs, C.byref(m)))
+        try:
+            n, nb, arr, o = int(m.n_logs), int(m.ops.n_logs), _copied, m.ops
+            chg_off = arr(o.chg_off, np.uint64, nb + 1)
+            op_off = arr(o.op_off, np.uint64, int(chg_off[nb]) + 1)
+            ni = int(op_off[-1])
+            ops = wire.InputOps(chg_off, op_off, arr(o.action, np.uint8, ni), arr(o.mark_type, np.uint8, ni), arr(o.index, np.uint32, ni), arr(o.count, np.uint32, ni),
+                                arr(o.payload, np.uint32, ni), arr(o.values, np.uint32, int(o.n_values)), None, int(o.max_actors))
+            return wire.ReplacePlan(status=arr(m.status, np.uint32, n), n_matches=arr(m.n_matches, np.uint32, n), n_chosen=arr(m.n_chosen, np.uint32, n),
+                                    n_replaced=arr(m.n_replaced, np.uint32, n), ops=ops, first_log=self.info()["first_log"], n_pattern=int(m.n_pattern),
+                                    n_replacement=int(m.n_replacement), kernel_ms=float(m.kernel_ms))
+        finally:
+            eng.lib.ptx_replace_plan_free(C.byref(m))
+
     def free(self):
         if self.handle is not None:
             self.engine.lib.ptx_text_view_free(self.engine.ctx, self.handle)
@@ -265,6 +287,26 @@ class Engine:
         h = C.c_void_p()
         self._check(self.lib.ptx_change(self.ctx, dbatch, dresult, C.byref(s), C.byref(h), status.ctypes.data_as(abi.u32p)))
         return h, status[: s.n_logs]
+
+    def replace_text(self, dbatch, dresult, view, batch, pattern, replacement_values, actors, ascii_nocase=False):
+        """Replace all on many replicas at once: TextView.replace_plan of `view` (a view of `dresult` = merge of `dbatch`, WITH elem_rank) made into Changes by
+        ptx_change.  replacement_values: the replacement's element strings (an editor passes list(text): bridge.ts:445), interned into batch.values as
+        wire.encode_input_ops does — upload the strings again before the next text query; actors[l] = the actor id of the replica behind log l of `batch`.
+        Returns (resident batch of the new Changes only, status per log of the batch from ptx_change, the wire.ReplacePlan)."""
+        value_ix = {v: i for i, v in enumerate(batch.values)}
+        ids = []
+        for v in replacement_values:
+            if not isinstance(v, str):
+                raise ValueError("Expected value inserted into text to be a string")
+            if v not in value_ix:
+                value_ix[v] = len(batch.values)
+                batch.values.append(v)
+            ids.append(value_ix[v])
+        plan = view.replace_plan(pattern, ids, batch.n_logs, ascii_nocase=ascii_nocase)
+        plan.ops.actor = np.asarray([batch.doc_actors[batch.log_doc[l]].index(actors[l]) for l in range(batch.n_logs)], dtype=np.uint32)
+        plan.ops.max_actors = max(batch.max_actors, max((len(a) for a in batch.doc_actors), default=1))
+        made, status = self.change(dbatch, dresult, plan.ops)
+        return made, status, plan
 
     def sync_replicas(self, dbatch, pairs, max_attempts=10001):
         """getMissingChanges + applyChanges (reference/test/merge.ts:4-38) for many replica pairs with the logs resident (ptx_sync_replicas):

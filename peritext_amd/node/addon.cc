@@ -102,6 +102,9 @@ struct Lib {
     ptx_status (*view_text_slices)(ptx_ctx*, const ptx_dview*, const uint64_t*, const uint32_t*, const uint32_t*, ptx_slices*) = nullptr;
     ptx_status (*view_find_snippets)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, ptx_snippets*) = nullptr;
     void (*snippets_free)(ptx_snippets*) = nullptr;
+    /* find and replace on a view: hits into change() input */
+    ptx_status (*view_replace_plan)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, ptx_replace_plan*) = nullptr;
+    void (*replace_plan_free)(ptx_replace_plan*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -154,7 +157,8 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.result_text_range, "ptx_result_text_range") && sym(L.text_free, "ptx_text_free") && sym(L.result_find_text, "ptx_result_find_text") &&
                   sym(L.matches_free, "ptx_matches_free") && sym(L.result_text_slices, "ptx_result_text_slices") && sym(L.slices_free, "ptx_slices_free") &&
                   sym(L.text_view_create, "ptx_text_view_create") && sym(L.text_view_free, "ptx_text_view_free") && sym(L.view_find_text, "ptx_view_find_text") &&
-                  sym(L.view_text_slices, "ptx_view_text_slices") && sym(L.view_find_snippets, "ptx_view_find_snippets") && sym(L.snippets_free, "ptx_snippets_free");
+                  sym(L.view_text_slices, "ptx_view_text_slices") && sym(L.view_find_snippets, "ptx_view_find_snippets") && sym(L.snippets_free, "ptx_snippets_free") &&
+                  sym(L.view_replace_plan, "ptx_view_replace_plan") && sym(L.replace_plan_free, "ptx_replace_plan_free");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -921,6 +925,42 @@ napi_value ViewFindSnippets(napi_env env, napi_callback_info info) {
     L.snippets_free(&m);
     return out;
 }
+/* viewReplacePlan(ctx, handle, pattern, flags, nReplacement) -> the plan of ptx_view_replace_plan over every log of the view: status, nMatches, nChosen, nReplaced
+ * (Uint32Array per log), chgOff, opOff (BigUint64Array), action (Uint8Array), index, count (Uint32Array).  The value ids of the inserts are not the addon's
+ * business: index.js writes the replacement's strings into the InputOperations itself, as bridge.ts:445 does */
+napi_value ViewReplacePlan(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 4 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewReplacePlan(ctx, handle, pattern: Uint16Array, flags, nReplacement): no live view");
+    const uint16_t* pat = nullptr;
+    uint32_t np = 0, flags = 0, nrep = 0;
+    if (!pattern_arg(env, argv[2], &pat, &np) || napi_get_value_uint32(env, argv[3], &flags) != napi_ok || napi_get_value_uint32(env, argv[4], &nrep) != napi_ok)
+        return throw_msg(env, "viewReplacePlan: pattern must be a Uint16Array, flags and nReplacement unsigned 32-bit numbers");
+    std::vector<uint32_t> ids(nrep <= PTX_CHANGE_ROWS_MAX ? nrep : 1u, 0u); /* (a longer replacement is the library's PTX_ERR_INVALID_ARG) */
+    ptx_replace_plan m;
+    const ptx_status st = L.view_replace_plan(ctx, h->view, pat, np, flags, ids.data(), nrep, h->n_logs, &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_replace_plan", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        const size_t nl = (size_t)m.n_logs, nb = (size_t)m.ops.n_logs, nc = (size_t)m.ops.chg_off[nb], ni = (size_t)m.ops.op_off[nc];
+        if ((v = make_u32(env, m.status, nl))) napi_set_named_property(env, out, "status", v);
+        if ((v = make_u32(env, m.n_matches, nl))) napi_set_named_property(env, out, "nMatches", v);
+        if ((v = make_u32(env, m.n_chosen, nl))) napi_set_named_property(env, out, "nChosen", v);
+        if ((v = make_u32(env, m.n_replaced, nl))) napi_set_named_property(env, out, "nReplaced", v);
+        if ((v = make_typed(env, napi_biguint64_array, 8, m.ops.chg_off, nb + 1))) napi_set_named_property(env, out, "chgOff", v);
+        if ((v = make_typed(env, napi_biguint64_array, 8, m.ops.op_off, nc + 1))) napi_set_named_property(env, out, "opOff", v);
+        if ((v = make_typed(env, napi_uint8_array, 1, m.ops.action, ni))) napi_set_named_property(env, out, "action", v);
+        if ((v = make_u32(env, m.ops.index, ni))) napi_set_named_property(env, out, "index", v);
+        if ((v = make_u32(env, m.ops.count, ni))) napi_set_named_property(env, out, "count", v);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.replace_plan_free(&m);
+    return out;
+}
 
 uint32_t u32_prop(napi_env env, napi_value obj, const char* name, uint32_t dflt) {
     napi_value v;
@@ -1540,7 +1580,8 @@ napi_value Init(napi_env env, napi_value exports) {
                                               {"viewFree", nullptr, ViewFree, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"viewFindText", nullptr, ViewFindText, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"viewTextSlices", nullptr, ViewTextSlices, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"viewFindSnippets", nullptr, ViewFindSnippets, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"viewFindSnippets", nullptr, ViewFindSnippets, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewReplacePlan", nullptr, ViewReplacePlan, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

@@ -113,7 +113,19 @@ export interface TextView {
     findText(needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number }): Array<Array<{ status: number; count: number; hits: Array<{ unit: number; startIndex: number; endIndex: number }> }>>
     textSlices(ranges: Array<Array<Array<{ startIndex: number; endIndex: number }>>>): Array<Array<Array<{ status: number; startIndex: number; endIndex: number; spans: FormatSpanWithText[] }>>>
     findSnippets(needle: string, opts?: { ignoreAsciiCase?: boolean; maxHits?: number; before?: number; after?: number }): Array<Array<{ status: number; count: number; snippets: Snippet[] }>>
+    /** replace all as change() input, planned on the device (ptx_view_replace_plan): the leftmost non-overlapping matches that cover whole elements, in
+     *  descending order, a delete and an insert of replacement.split("") each; calls for changeMany = plan.map(logs => logs.map(x => (x.ops.length ? [x.ops] : []))) */
+    replacePlan(needle: string, replacement: string, opts?: { asciiNocase?: boolean }): Array<Array<ReplacePlanOfLog>>
     free(): void
+}
+export interface ReplacePlanOfLog {
+    log: number
+    /** the replica's merge / text status, or 5 (PTX_ERR_CAPACITY) where the Change would make more than 65 534 ops: then `ops` is empty */
+    status: number
+    nMatches: number
+    nChosen: number
+    nReplaced: number
+    ops: InputOperation[]
 }
 export class MergeEngine {
     /** resident (default true): the logs of a document's replica() handles stay in HBM between calls — a read encodes and uploads only the Changes that

@@ -42,6 +42,8 @@ const CHG_ACTOR_SHIFT = 20, CHG_NOPS = 0x000fffff, ENV_SATURATED = 65535
 const VERSION_ALL = 0xffffffff /* PTX_VERSION_ALL: a clock entry that keeps every change of the actor */
 const FIND_PATTERN_MAX = 256 /* PTX_FIND_PATTERN_MAX: code units of a needle */
 const FIND_ASCII_NOCASE = 1 /* PTX_FIND_ASCII_NOCASE */
+const CHANGE_ROWS_MAX = 65534 /* PTX_CHANGE_ROWS_MAX: rows the Changes of one replica may make in one change call */
+const IN_DELETE = 1 /* PTX_IN_DELETE (a plan's other action is PTX_IN_INSERT = 0) */
 const envStride = maxActors => (1 + maxActors + 3) & ~3 /* PTX_ENV_STRIDE */
 
 /** chgActor / chgSeq / chgNops / chgDeps -> the packed envelope the device reads: chgHdr = actor << 20 | nops, chgEnv rows of
@@ -978,6 +980,12 @@ class MergeEngine {
      *                                default 0; clamped as Array.prototype.slice clamps) in ONE device call: per document and replica { status, count, snippets },
      *                                a snippet being { log, hitStart, hitEnd, text, matchUnit, spans } — text.substr(matchUnit, needle.length) is the match (highlight
      *                                it), spans the FormatSpanWithText[] of the snippet.  opts.ignoreAsciiCase and opts.maxHits as findText
+     *    replacePlan(needle, replacement, opts)  replace all as change() input, planned on the device (ptx_view_replace_plan): per document and replica { log,
+     *                                status, nMatches, nChosen, nReplaced, ops: InputOperation[] }.  The matches String.prototype.replaceAll(needle, ...) would
+     *                                replace are chosen — leftmost, non-overlapping —; those that cover whole elements give, in descending order, a delete and
+     *                                (for a non-empty replacement) an insert of replacement.split("") at the same index (bridge.ts:425-446); one that starts or
+     *                                ends inside a multi-unit element is skipped (nChosen - nReplaced).  opts.asciiNocase as ignoreAsciiCase.  The result is
+     *                                ready for changeMany: calls = plan.map(logs => logs.map(x => (x.ops.length ? [x.ops] : [])))
      *    free()                      releases the device memory; the view is unusable afterwards */
     textView(docs) {
         const batch = encodeDocs(docs)
@@ -1026,6 +1034,23 @@ class MergeEngine {
                         snippets.push({ log: l, hitStart: m.hitStart[k], hitEnd: m.hitEnd[k], text: cut.text, matchUnit: m.matchUnit[k], spans: cut.spans })
                     }
                     return { status: m.status[l], count: m.nMatches[l], snippets }
+                }))
+            },
+            replacePlan(needle, replacement, opts) {
+                if (typeof replacement !== "string" || replacement.length > CHANGE_ROWS_MAX) throw new RangeError("replacement: a string of at most " + CHANGE_ROWS_MAX + " UTF-16 code units")
+                const a = findArgs(needle, opts && { ignoreAsciiCase: opts.asciiNocase || opts.ignoreAsciiCase })
+                const values = replacement.split("") /* one element per code unit, as bridge.ts:445 */
+                const m = engine.addon.viewReplacePlan(engine.ctx, live(), a.pattern, a.flags, values.length)
+                let log = 0
+                return docs.map(logs => logs.map(() => {
+                    const l = log++, ops = []
+                    for (let c = Number(m.chgOff[l]); c < Number(m.chgOff[l + 1]); c++) {
+                        for (let q = Number(m.opOff[c]); q < Number(m.opOff[c + 1]); q++) {
+                            if (m.action[q] === IN_DELETE) ops.push({ path: ["text"], action: "delete", index: m.index[q], count: m.count[q] })
+                            else ops.push({ path: ["text"], action: "insert", index: m.index[q], values: values.slice() })
+                        }
+                    }
+                    return { log: l, status: m.status[l], nMatches: m.nMatches[l], nChosen: m.nChosen[l], nReplaced: m.nReplaced[l], ops }
                 }))
             },
             free() {

@@ -584,6 +584,59 @@ def encode_input_ops(batch, per_log, actors):
                     u32(index), u32(count), u32(payload), u32(values), u32(actor), max(batch.max_actors, max((len(a) for a in batch.doc_actors), default=1)))
 
 
+def decode_input_ops(ops, values):
+    """The inverse of encode_input_ops for inserts and deletes on the text list: per log of `ops` (InputOps) the change() calls it holds, each a list of the
+    reference's InputOperation dicts; `values` = the string table the value ids point into (batch.values)."""
+    per_log = []
+    for l in range(len(ops.chg_off) - 1):
+        calls = []
+        for c in range(int(ops.chg_off[l]), int(ops.chg_off[l + 1])):
+            call = []
+            for q in range(int(ops.op_off[c]), int(ops.op_off[c + 1])):
+                a, i, n, p = int(ops.action[q]), int(ops.index[q]), int(ops.count[q]), int(ops.payload[q])
+                if a == abi.IN_INSERT:
+                    call.append({"path": ["text"], "action": "insert", "index": i, "values": [values[int(v)] for v in ops.values[p : p + n]]})
+                elif a == abi.IN_DELETE:
+                    call.append({"path": ["text"], "action": "delete", "index": i, "count": n})
+                else:
+                    raise ValueError("InputOperation action %d is no insert or delete" % a)
+            calls.append(call)
+        per_log.append(calls)
+    return per_log
+
+
+@dataclass
+class ReplacePlan:
+    """Host view of ptx_replace_plan (TextView.replace_plan): per log of the VIEW its matches, the greedy non-overlapping ones of them (n_chosen) and those of
+    these that cover whole elements (n_replaced); `ops` holds the InputOperations that replace the latter — one Change per log that has any, its matches in
+    descending order, a delete and (with a replacement) an insert each — over the n_batch_logs logs of the batch: view log l is batch log first_log + l.
+    ops.actor / ops.max_actors are the caller's to fill in (Engine.replace_text does)."""
+
+    status: np.ndarray  # u32 [n_logs] the view's, or ERR_CAPACITY
+    n_matches: np.ndarray  # u32 [n_logs]
+    n_chosen: np.ndarray  # u32 [n_logs]
+    n_replaced: np.ndarray  # u32 [n_logs]
+    ops: InputOps
+    first_log: int = 0
+    n_pattern: int = 0
+    n_replacement: int = 0
+    kernel_ms: float = 0.0
+
+    def per_log(self, values):
+        """decode_input_ops of the plan: per BATCH log its change() calls (none or one) as InputOperation dicts."""
+        return decode_input_ops(self.ops, values)
+
+    def ops_of_log(self, log, values):
+        """The InputOperation dicts of VIEW log `log` ([] where it makes no Change)."""
+        calls = decode_input_ops(_ops_of_one_log(self.ops, self.first_log + log), values)[0]
+        return calls[0] if calls else []
+
+
+def _ops_of_one_log(ops, l):
+    """`ops` cut down to its log l (the arrays are shared; chg_off keeps the Change's number)."""
+    return InputOps(ops.chg_off[l : l + 2], ops.op_off, ops.action, ops.mark_type, ops.index, ops.count, ops.payload, ops.values, ops.actor, ops.max_actors)
+
+
 @dataclass
 class Results:
     """Host view of a merge result: numpy arrays, row r of log l at log_off[l] + r."""
