@@ -864,6 +864,46 @@ ptx_status ptx_view_replace_plan(ptx_ctx* ctx, const ptx_dview* v, const uint16_
                                  uint32_t n_replacement, uint32_t n_batch_logs, ptx_replace_plan* out);
 void ptx_replace_plan_free(ptx_replace_plan* m);
 
+/* ---- InputOperations as a resident object: change() without the host in between ----
+ * ptx_change takes its InputOperations from host memory: it walks every op and every offset there, downloads the headers of the base batch to size its launch
+ * and uploads the ops.  A ptx_dinput_ops holds the same eleven arrays in device memory, and ptx_change_device does the walks there.
+ *   ptx_input_ops_upload       copies the arrays of `host` (one copy out of pinned memory where they are small).  It reads chg_off[n_logs] and
+ *                              op_off[n_changes] to learn the sizes and validates nothing else; chg_off / op_off / actor (n_logs > 0) and the five op columns
+ *                              (n_input_ops > 0) must not be NULL.  Synchronises: the caller's arrays are free to go
+ *   ptx_input_ops_wrap_device  adopts DEVICE columns the caller owns (torch tensors, say) and copies nothing: they must outlive the object and every call that
+ *                              takes it.  The library cannot read the sizes, so they are arguments; n_values is the struct's field.  chg_off must hold
+ *                              n_logs + 1 entries, op_off n_changes + 1, the op columns n_input_ops
+ *   ptx_input_ops_download     a host copy, library-owned until ptx_host_input_ops_free
+ *   ptx_change_device          ptx_change on the same arrays: the same call status, the same status_out, a `made` batch equal column for column, envelope and
+ *                              headers included.  The argument errors ptx_change finds by walking the arrays — chg_off / op_off not starting at 0 or
+ *                              decreasing, an insert pointing outside `values`, more than PTX_CHANGE_ROWS_MAX rows for one log — are found on the device and
+ *                              fail the whole call with PTX_ERR_INVALID_ARG at its first wait, before any output is allocated: *made = NULL, status_out
+ *                              untouched, ptx_last_error names the lowest offending entry or log.  One check more than ptx_change's, because the sizes of a
+ *                              wrapped object are the caller's word: chg_off and op_off must END at n_changes and n_input_ops (PTX_ERR_INVALID_ARG; nothing is
+ *                              read behind the columns in either case).  Three waits; between them nothing proportional to the ops or to the base batch's logs
+ *                              crosses PCIe except status_out
+ *   ptx_view_replace_plan_device  ptx_view_replace_plan with the ops left where the passes wrote them: status and the three count arrays come down in
+ *                              `counts` (the pointers of counts->ops stay NULL; its n_logs, n_values and max_actors are filled), the op columns, chg_off,
+ *                              op_off and the replacement's value ids stay on the device in *ops, with `actor` (HOST, [n_batch_logs], copied) and max_actors.
+ *                              The argument errors of ptx_view_replace_plan, and a NULL `actor` with n_batch_logs > 0.  Free `counts` with
+ *                              ptx_replace_plan_free and *ops with ptx_input_ops_free */
+typedef struct ptx_dinput_ops ptx_dinput_ops;
+typedef struct ptx_host_input_ops {
+    ptx_input_ops ops;             /* HOST pointers into a library-owned block */
+    uint64_t n_changes;
+    uint64_t n_input_ops;
+    void* owner;
+} ptx_host_input_ops;
+ptx_status ptx_input_ops_upload(ptx_ctx* ctx, const ptx_input_ops* host, ptx_dinput_ops** out);
+ptx_status ptx_input_ops_wrap_device(ptx_ctx* ctx, const ptx_input_ops* device_columns, uint64_t n_changes, uint64_t n_input_ops, ptx_dinput_ops** out);
+ptx_status ptx_input_ops_download(ptx_ctx* ctx, const ptx_dinput_ops* d, ptx_host_input_ops* out);
+void ptx_host_input_ops_free(ptx_host_input_ops* h);
+void ptx_input_ops_free(ptx_ctx* ctx, ptx_dinput_ops* d);
+ptx_status ptx_change_device(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* merged, const ptx_dinput_ops* in, ptx_dbatch** made, uint32_t* status_out);
+ptx_status ptx_view_replace_plan_device(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement,
+                                        uint32_t n_replacement, uint32_t n_batch_logs, const uint32_t* actor /* host, [n_batch_logs] */, uint32_t max_actors,
+                                        ptx_replace_plan* counts, ptx_dinput_ops** ops);
+
 /* Copy a resident batch back to the host (columns, envelope, headers; library-owned until ptx_host_batch_free). */
 typedef struct ptx_host_batch {
     ptx_batch b;

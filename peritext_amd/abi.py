@@ -255,6 +255,10 @@ class ptx_host_batch(C.Structure):
     _fields_ = [("b", ptx_batch), ("owner", C.c_void_p)]
 
 
+class ptx_host_input_ops(C.Structure):  # ptx_input_ops_download: a host copy of resident InputOperations
+    _fields_ = [("ops", ptx_input_ops), ("n_changes", C.c_uint64), ("n_input_ops", C.c_uint64), ("owner", C.c_void_p)]
+
+
 # the merge kernel's last phase (LWW winners, spans; peritext_amd/csrc/merge_core.h)
 LWW_TILE_4 = 128  # PTX_TILE_4: visible chars up to which the four LWW trees are resident at once (twice that with a tree per present type)
 LWW_TILE_1 = 512  # PTX_TILE_1: tile of the visible axis for longer documents (twice that where the launch's LDS window has room)
@@ -484,6 +488,13 @@ FUNCTIONS = {
     "ptx_snippets_free": (None, [C.POINTER(ptx_snippets)]),
     "ptx_view_replace_plan": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.POINTER(ptx_replace_plan)]),
     "ptx_replace_plan_free": (None, [C.POINTER(ptx_replace_plan)]),
+    "ptx_input_ops_upload": (C.c_int32, [vp, C.POINTER(ptx_input_ops), C.POINTER(vp)]),
+    "ptx_input_ops_wrap_device": (C.c_int32, [vp, C.POINTER(ptx_input_ops), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "ptx_input_ops_download": (C.c_int32, [vp, vp, C.POINTER(ptx_host_input_ops)]),
+    "ptx_host_input_ops_free": (None, [C.POINTER(ptx_host_input_ops)]),
+    "ptx_input_ops_free": (None, [vp, vp]),
+    "ptx_change_device": (C.c_int32, [vp, vp, vp, vp, C.POINTER(vp), u32p]),
+    "ptx_view_replace_plan_device": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.POINTER(ptx_replace_plan), C.POINTER(vp)]),
     "ptx_max_ops_per_log": (C.c_uint32, [vp]),
     "ptx_kernel_name": (C.c_char_p, []),
     "ptx_batch_kernel_name": (C.c_char_p, [vp, vp]),

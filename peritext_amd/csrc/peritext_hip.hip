@@ -32,6 +32,7 @@
 #include "replay_hbm_core.h"
 #include "gen_core.h"
 #include "change_core.h"
+#include "change_prep_core.h"
 #include "cursor_core.h"
 #include "rootmap_core.h"
 #include "sync_core.h"
@@ -196,6 +197,16 @@ extern "C" __global__ void __launch_bounds__(64) ptx_gen_kernel_r8(PtxGenArgs A)
 extern "C" __global__ void __launch_bounds__(64) ptx_change_kernel(PtxChangeArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ptx_lds[];
     if (blockIdx.x < A.n_logs) ptx_change_log<64>(A, blockIdx.x, ptx_lds);
+}
+/* ... and its preparation for InputOperations that are resident (change_prep_core.h): a lane per entry of the two offset arrays checks them, one wave per log
+ * counts the rows its Changes will make, checks its inserts against `values` and folds its LDS need into the launch's */
+extern "C" __global__ void __launch_bounds__(256) ptx_change_offsets_check_kernel(PtxChangePrepArgs A) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < ptx_change_offsets_entries(A)) ptx_change_offsets_check_one(A, i);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_change_prep_kernel(PtxChangePrepArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t ptx_prep_lds[PTX_CHANGE_PREP_LDS_BYTES];
+    if (blockIdx.x < A.n_logs) ptx_change_prep_log<64>(A, blockIdx.x, ptx_prep_lds);
 }
 
 /* the sync between two replicas (sync_core.h): one wave per pair plans (missing changes in retry order), one workgroup per pair gathers their rows */
@@ -899,6 +910,18 @@ struct ptx_dresult {
     uint32_t* rank = nullptr;
     uint32_t* refs = nullptr; /* with rank: resolved references of the delete / mark rows (PtxMergeArgs.out_refs), for ptx_replay_patches */
     uint32_t* refs_hi = nullptr; /* with refs, for a batch that holds a log of more than 32 766 list elements: the high halves of its mark rows' boundary slots */
+};
+
+/* InputOperations resident in HBM (ptx_input_ops_upload / _wrap_device / ptx_view_replace_plan_device): the columns of ptx_input_ops as device pointers, and
+ * the sizes the host cannot read off them.  A column is NULL where the caller's was (ptx_change_device refuses what ptx_change refuses) */
+struct ptx_dinput_ops {
+    uint32_t n_logs = 0, max_actors = 0;
+    uint64_t n_changes = 0, n_input_ops = 0, n_values = 0;
+    bool owns = true;                              /* false: ptx_input_ops_wrap_device, the columns are the caller's */
+    void* blocks[3] = {nullptr, nullptr, nullptr}; /* owned device blocks the pointers below point into */
+    uint64_t *chg_off = nullptr, *op_off = nullptr;
+    uint8_t *action = nullptr, *mark_type = nullptr;
+    uint32_t *index = nullptr, *count = nullptr, *payload = nullptr, *values = nullptr, *actor = nullptr;
 };
 
 static std::mutex g_index_mu;                        /* the index_state / index_stream / index_ev of every batch */
@@ -3071,7 +3094,10 @@ void ptx_replace_plan_free(ptx_replace_plan* m) {
 /* the arguments are checked; h->pinned[0]: status | n_matches | n_chosen | n_replaced | hit_off (scratch) | chg_off,  h->pinned[1]: op_off | index | count | payload |
  * action | mark_type | values */
 static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement, uint32_t n_replacement,
-                                    uint32_t n_batch_logs, ptx_host_result* h, ptx_replace_plan* out) {
+                                    uint32_t n_batch_logs, ptx_host_result* h, ptx_replace_plan* out, ptx_dinput_ops* keep = nullptr, const uint32_t* actor = nullptr,
+                                    uint32_t max_actors = 0) {
+    /* `keep` (ptx_view_replace_plan_device): the same passes; the op columns, chg_off and op_off are not brought down — their blocks are handed to `keep`, with
+     * a third block that holds a zero (the op_off of a plan without ops), `actor` and the replacement's value ids */
     PTX_HIP(ctx, ptx_enter(ctx));
     const uint32_t n_logs = v->n_logs;
     const uint64_t no = (uint64_t)n_logs + 1, nbo = (uint64_t)n_batch_logs + 1;
@@ -3079,10 +3105,28 @@ static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint
     /* block 0, device and pinned host alike: status | n_matches | n_chosen | n_replaced | hit_off | chg_off — what comes down — | n_ops | makes | op_log_off | the pattern */
     const uint64_t st_bytes = a16((uint64_t)n_logs * 4), ho_at = 4 * st_bytes, co_at = ho_at + a16(no * 8), down0 = co_at + a16(nbo * 8);
     const uint64_t no_at = down0, mk_at = no_at + st_bytes, ol_at = mk_at + a16((uint64_t)n_batch_logs * 4), pat_at = ol_at + a16(no * 8), blk0 = pat_at + a16((uint64_t)n_pattern * 2);
-    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
     hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
     h->pinned[0] = hp0;
     if (e == hipSuccess) e = ptx_dev_malloc((void**)&d0, blk0);
+    const uint64_t act_at = 16, rv_at = act_at + a16((uint64_t)n_batch_logs * 4), blk3 = rv_at + a16((uint64_t)n_replacement * 4) + 16;
+    if (keep) { /* the third block goes up first, through the context's pinned staging; chg_off of a view without hits is zeroed where the scan would write it */
+        if (e == hipSuccess && ctx->up_h_cap < blk3) {
+            if (ctx->up_h) (void)hipHostFree(ctx->up_h);
+            ctx->up_h = nullptr;
+            ctx->up_h_cap = 0;
+            e = hipHostMalloc((void**)&ctx->up_h, 2 * blk3, hipHostMallocDefault);
+            if (e == hipSuccess) ctx->up_h_cap = 2 * blk3;
+        }
+        if (e == hipSuccess) e = ptx_dev_malloc((void**)&d3, blk3);
+        if (e == hipSuccess) {
+            memset(ctx->up_h, 0, 16);
+            if (n_batch_logs) memcpy(ctx->up_h + act_at, actor, (size_t)n_batch_logs * 4);
+            if (n_replacement) memcpy(ctx->up_h + rv_at, replacement, (size_t)n_replacement * 4);
+            e = hipMemcpyAsync(d3, ctx->up_h, blk3 - 16, hipMemcpyHostToDevice, ctx->stream);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(d0 + co_at, 0, nbo * 8, ctx->stream);
+    }
     float ms[3] = {0.f, 0.f, 0.f};
     uint64_t nhits = 0, sizes[2] = {0, 0}; /* Changes, InputOperations */
     bool too_many = false;
@@ -3162,9 +3206,9 @@ static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint
     /* block 2, device and pinned host alike: op_off | index | count | payload | action | mark_type; the host's goes on with the value ids */
     const uint64_t nc = sizes[0], ni = sizes[1], oo_bytes = a16((nc + 1) * 8), c4 = a16(ni * 4), c1 = a16(ni), val_at = oo_bytes + 3 * c4 + 2 * c1,
                    blk2 = val_at + a16((uint64_t)n_replacement * 4) + 16;
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
+    if (e == hipSuccess && !keep) e = hipHostMalloc((void**)&hp1, blk2, hipHostMallocDefault);
     h->pinned[1] = hp1;
-    if (e == hipSuccess) {
+    if (e == hipSuccess && !keep) {
         memset(hp1, 0, oo_bytes); /* no Change: op_off = {0} */
         if (n_replacement) memcpy(hp1 + val_at, replacement, (size_t)n_replacement * 4); /* the caller's ids are free to go */
     }
@@ -3184,19 +3228,44 @@ static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hp1, d2, val_at, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && !keep) e = hipMemcpyAsync(hp1, d2, val_at, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess && nhits) { /* the plan's status and counts, and chg_off: with the ops, one wait */
         e = hipMemcpyAsync(hp0, d0, st_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(hp0 + 2 * st_bytes, d0 + 2 * st_bytes, 2 * st_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + co_at, d0 + co_at, nbo * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && !keep) e = hipMemcpyAsync(hp0 + co_at, d0 + co_at, nbo * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         else (void)hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess && ni) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
+    } else if (keep) { /* (the staging block is free again when the call returns) */
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (keep && e == hipSuccess) { /* the blocks are handed over, not copied and freed */
+        keep->n_logs = n_batch_logs;
+        keep->max_actors = max_actors;
+        keep->n_changes = nc;
+        keep->n_input_ops = ni;
+        keep->n_values = n_replacement;
+        keep->owns = true;
+        keep->blocks[0] = d0;
+        keep->blocks[1] = d2;
+        keep->blocks[2] = d3;
+        keep->chg_off = (uint64_t*)(d0 + co_at);
+        keep->op_off = ni ? (uint64_t*)d2 : (uint64_t*)d3;
+        keep->index = ni ? R.index : nullptr;
+        keep->count = ni ? R.count : nullptr;
+        keep->payload = ni ? R.payload : nullptr;
+        keep->action = ni ? R.action : nullptr;
+        keep->mark_type = ni ? R.mark_type : nullptr;
+        keep->actor = (uint32_t*)(d3 + act_at);
+        keep->values = (uint32_t*)(d3 + rv_at);
+        d0 = d2 = d3 = nullptr;
     }
     (void)ptx_dev_free(d0);
     (void)ptx_dev_free(d1);
     (void)ptx_dev_free(d2);
+    (void)ptx_dev_free(d3);
     if (e != hipSuccess) {
         if (too_many) return fail(ctx, PTX_ERR_CAPACITY, "more than 2^32 - 1 matches in the view: plan a smaller range");
         return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view replace plan: ") + hipGetErrorString(e));
@@ -3210,6 +3279,11 @@ static ptx_status view_replace_impl(ptx_ctx* ctx, const ptx_dview* v, const uint
     out->n_chosen = (const uint32_t*)(hp0 + 2 * st_bytes);
     out->n_replaced = (const uint32_t*)(hp0 + 3 * st_bytes);
     out->ops.n_logs = n_batch_logs;
+    out->ops.n_values = n_replacement;
+    if (keep) { /* the ops stay on the device: no pointer of out->ops is set */
+        out->ops.max_actors = max_actors;
+        return PTX_OK;
+    }
     out->ops.max_actors = 0;
     out->ops.chg_off = (const uint64_t*)(hp0 + co_at);
     out->ops.op_off = (const uint64_t*)hp1;
@@ -3241,6 +3315,31 @@ ptx_status ptx_view_replace_plan(ptx_ctx* ctx, const ptx_dview* v, const uint16_
         return st;
     }
     out->owner = h;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_replace_plan_device(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, const uint32_t* replacement, uint32_t n_replacement,
+                                        uint32_t n_batch_logs, const uint32_t* actor, uint32_t max_actors, ptx_replace_plan* counts, ptx_dinput_ops** ops) {
+    if (!ctx || !v || !counts || !ops) return PTX_ERR_INVALID_ARG;
+    memset(counts, 0, sizeof(*counts));
+    *ops = nullptr;
+    ptx_status st = view_find_check(ctx, pattern, n_pattern, flags);
+    if (st != PTX_OK) return st;
+    if (n_replacement > PTX_CHANGE_ROWS_MAX) return fail(ctx, PTX_ERR_INVALID_ARG, "replacement of more than PTX_CHANGE_ROWS_MAX elements");
+    if (n_replacement && !replacement) return fail(ctx, PTX_ERR_INVALID_ARG, "replacement is NULL");
+    if ((uint64_t)n_batch_logs < (uint64_t)v->first_log + v->n_logs) return fail(ctx, PTX_ERR_INVALID_ARG, "n_batch_logs ends before the view's range");
+    if (n_batch_logs && !actor) return fail(ctx, PTX_ERR_INVALID_ARG, "actor is NULL");
+    ptx_host_result* h = new ptx_host_result();
+    ptx_dinput_ops* d = new ptx_dinput_ops();
+    st = view_replace_impl(ctx, v, pattern, n_pattern, flags, replacement, n_replacement, n_batch_logs, h, counts, d, actor, max_actors);
+    if (st != PTX_OK) {
+        delete h;
+        delete d;
+        memset(counts, 0, sizeof(*counts));
+        return st;
+    }
+    counts->owner = h;
+    *ops = d;
     return PTX_OK;
 }
 
@@ -4530,6 +4629,386 @@ ptx_status ptx_change(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* m
         PTX_TRYC(hipStreamSynchronize(ctx->stream));
     }
 #undef PTX_TRYC
+    drop();
+    const ptx_status st = census_and_shape(ctx, b, false);
+    if (st != PTX_OK) {
+        ptx_batch_free(ctx, b);
+        return st;
+    }
+    *made = b;
+    return PTX_OK;
+}
+
+/* ---- InputOperations as a resident object, and change() from them (change_prep_core.h) ---- */
+void ptx_input_ops_free(ptx_ctx* ctx, ptx_dinput_ops* d) {
+    if (!d) return;
+    if (ctx) (void)ptx_enter(ctx);
+    if (d->owns)
+        for (void* p : d->blocks) (void)ptx_dev_free(p);
+    delete d;
+}
+
+ptx_status ptx_input_ops_upload(ptx_ctx* ctx, const ptx_input_ops* in, ptx_dinput_ops** out) {
+    if (!ctx || !in || !out) return PTX_ERR_INVALID_ARG;
+    *out = nullptr;
+    const uint32_t L = in->n_logs;
+    if (L && (!in->chg_off || !in->op_off || !in->actor)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_input_ops_upload: chg_off / op_off / actor is NULL");
+    /* the sizes, read where ptx_change reads them; nothing else is looked at (ptx_change_device checks on the device what ptx_change checks on the host) */
+    const uint64_t NC = L ? in->chg_off[L] : 0;
+    const uint64_t NI = NC ? in->op_off[NC] : 0;
+    if (NI && (!in->action || !in->mark_type || !in->index || !in->count || !in->payload)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_input_ops_upload: an InputOperation column is NULL");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    ptx_dinput_ops* d = new ptx_dinput_ops();
+    d->n_logs = L;
+    d->max_actors = in->max_actors;
+    d->n_changes = NC;
+    d->n_input_ops = NI;
+    d->n_values = in->n_values;
+    struct Piece {
+        void** dst;
+        const void* src;
+        size_t bytes;
+    };
+    const Piece pieces[] = {{(void**)&d->chg_off, in->chg_off, in->chg_off ? ((size_t)L + 1) * 8 : 0}, {(void**)&d->op_off, in->op_off, in->op_off ? ((size_t)NC + 1) * 8 : 0}, {(void**)&d->index, in->index, (size_t)NI * 4},
+                            {(void**)&d->count, in->count, (size_t)NI * 4}, {(void**)&d->payload, in->payload, (size_t)NI * 4},
+                            {(void**)&d->values, in->values, in->values ? (size_t)in->n_values * 4 : 0}, {(void**)&d->actor, in->actor, (size_t)L * 4},
+                            {(void**)&d->action, in->action, (size_t)NI}, {(void**)&d->mark_type, in->mark_type, (size_t)NI}};
+    size_t total = 0;
+    for (const Piece& q : pieces) total += (std::max<size_t>(q.bytes, 1) + 15) & ~(size_t)15;
+    uint8_t* blk = nullptr;
+    hipError_t e = ptx_dev_malloc((void**)&blk, total);
+    d->blocks[0] = blk;
+    const bool small = total <= (1u << 20); /* the eleven arrays of an edit go up as ONE copy out of pinned memory, as ptx_change sends them */
+    if (e == hipSuccess && small && ctx->up_h_cap < total) {
+        if (ctx->up_h) (void)hipHostFree(ctx->up_h);
+        ctx->up_h = nullptr;
+        ctx->up_h_cap = 0;
+        e = hipHostMalloc((void**)&ctx->up_h, 2 * total, hipHostMallocDefault);
+        if (e == hipSuccess) ctx->up_h_cap = 2 * total;
+    }
+    size_t at = 0;
+    for (const Piece& q : pieces) {
+        if (e != hipSuccess) break;
+        /* a column the caller left NULL stays NULL (values: "an insert points outside `values`" is the device's to find), an empty one points at its own 16 bytes */
+        *q.dst = q.src ? (void*)(blk + at) : nullptr;
+        if (q.bytes && small) memcpy(ctx->up_h + at, q.src, q.bytes);
+        else if (q.bytes) e = hipMemcpyAsync(blk + at, q.src, q.bytes, hipMemcpyHostToDevice, ctx->stream);
+        at += (std::max<size_t>(q.bytes, 1) + 15) & ~(size_t)15;
+    }
+    if (e == hipSuccess && small) e = hipMemcpyAsync(blk, ctx->up_h, total, hipMemcpyHostToDevice, ctx->stream);
+    { /* the caller's arrays and the staging block are free to go when the call returns */
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (e != hipSuccess) {
+        ptx_input_ops_free(ctx, d);
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("ptx_input_ops_upload: ") + hipGetErrorString(e));
+    }
+    *out = d;
+    return PTX_OK;
+}
+
+ptx_status ptx_input_ops_wrap_device(ptx_ctx* ctx, const ptx_input_ops* dev, uint64_t n_changes, uint64_t n_input_ops, ptx_dinput_ops** out) {
+    if (!ctx || !dev || !out) return PTX_ERR_INVALID_ARG;
+    *out = nullptr;
+    ptx_dinput_ops* d = new ptx_dinput_ops();
+    d->owns = false;
+    d->n_logs = dev->n_logs;
+    d->max_actors = dev->max_actors;
+    d->n_changes = n_changes;
+    d->n_input_ops = n_input_ops;
+    d->n_values = dev->n_values;
+    d->chg_off = (uint64_t*)dev->chg_off;
+    d->op_off = (uint64_t*)dev->op_off;
+    d->action = (uint8_t*)dev->action;
+    d->mark_type = (uint8_t*)dev->mark_type;
+    d->index = (uint32_t*)dev->index;
+    d->count = (uint32_t*)dev->count;
+    d->payload = (uint32_t*)dev->payload;
+    d->values = (uint32_t*)dev->values;
+    d->actor = (uint32_t*)dev->actor;
+    *out = d;
+    return PTX_OK;
+}
+
+struct PtxHostInputOpsOwner {
+    uint8_t* block = nullptr;
+    ~PtxHostInputOpsOwner() { free(block); }
+};
+void ptx_host_input_ops_free(ptx_host_input_ops* h) {
+    if (!h) return;
+    delete (PtxHostInputOpsOwner*)h->owner;
+    memset(h, 0, sizeof(*h));
+}
+ptx_status ptx_input_ops_download(ptx_ctx* ctx, const ptx_dinput_ops* d, ptx_host_input_ops* out) {
+    if (!ctx || !d || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    const uint32_t L = d->n_logs;
+    const uint64_t NC = d->n_changes, NI = d->n_input_ops;
+    if (L && (!d->chg_off || !d->op_off || !d->actor)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_input_ops_download: chg_off / op_off / actor is NULL");
+    if (NI && (!d->action || !d->mark_type || !d->index || !d->count || !d->payload)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_input_ops_download: an InputOperation column is NULL");
+    PTX_HIP(ctx, ptx_enter(ctx));
+    struct Piece {
+        const void** dst;
+        const void* src;
+        size_t bytes;
+    };
+    ptx_input_ops& o = out->ops;
+    const Piece pieces[] = {{(const void**)&o.chg_off, d->chg_off, d->chg_off ? ((size_t)L + 1) * 8 : 0}, {(const void**)&o.op_off, d->op_off, d->op_off ? ((size_t)NC + 1) * 8 : 0}, {(const void**)&o.index, d->index, (size_t)NI * 4},
+                            {(const void**)&o.count, d->count, (size_t)NI * 4}, {(const void**)&o.payload, d->payload, (size_t)NI * 4},
+                            {(const void**)&o.values, d->values, d->values ? (size_t)d->n_values * 4 : 0}, {(const void**)&o.actor, d->actor, (size_t)L * 4},
+                            {(const void**)&o.action, d->action, (size_t)NI}, {(const void**)&o.mark_type, d->mark_type, (size_t)NI}};
+    size_t total = 0;
+    for (const Piece& q : pieces) total += (std::max<size_t>(q.bytes, 1) + 15) & ~(size_t)15;
+    PtxHostInputOpsOwner* own = new PtxHostInputOpsOwner();
+    own->block = (uint8_t*)calloc(total, 1);
+    hipError_t e = own->block ? hipSuccess : hipErrorOutOfMemory;
+    size_t at = 0;
+    for (const Piece& q : pieces) {
+        if (e != hipSuccess) break;
+        *q.dst = q.src ? (const void*)(own->block + at) : nullptr;
+        if (q.bytes) e = hipMemcpyAsync(own->block + at, q.src, q.bytes, hipMemcpyDeviceToHost, ctx->stream);
+        at += (std::max<size_t>(q.bytes, 1) + 15) & ~(size_t)15;
+    }
+    {
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (e != hipSuccess) {
+        delete own;
+        memset(out, 0, sizeof(*out));
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("ptx_input_ops_download: ") + hipGetErrorString(e));
+    }
+    o.n_logs = L;
+    o.max_actors = d->max_actors;
+    o.n_values = d->n_values;
+    out->n_changes = NC;
+    out->n_input_ops = NI;
+    out->owner = own;
+    return PTX_OK;
+}
+
+/* ptx_change for resident InputOperations.  Three waits: the verdict of the prepare passes with the totals and the LDS need; the per-log status with the sizes
+ * of the made batch; the made batch.  Between them nothing proportional to the ops or to the base batch's logs crosses PCIe except status_out */
+ptx_status ptx_change_device(ptx_ctx* ctx, const ptx_dbatch* base, const ptx_dresult* merged, const ptx_dinput_ops* in, ptx_dbatch** made, uint32_t* status_out) {
+    if (!ctx || !base || !merged || !in || !made || !status_out) return PTX_ERR_INVALID_ARG;
+    *made = nullptr;
+    const uint32_t L = base->n_logs;
+    if (in->n_logs != L) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: the InputOperations must name every log of the base batch (a log may make no change)");
+    if (merged->n_logs != L || merged->n_rows != base->n_ops) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: `merged` is not the result of this batch");
+    if (!merged->rank) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change needs the elem_rank column (context created with PTX_FLAG_NO_ELEM_RANK)");
+    if (L && (!in->chg_off || !in->op_off || !in->actor)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: chg_off / op_off / actor is NULL");
+    if (base->n_ops && !base->chg_off) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change needs the Change envelope of the base batch (the replicas' clocks)");
+    const uint32_t na = base->chg_off && base->n_changes ? base->max_actors : in->max_actors;
+    if (na == 0 || na > 4096u || (base->chg_off && base->n_changes && in->max_actors && in->max_actors != base->max_actors))
+        return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: max_actors must be 1..4096 and equal to the base batch's");
+    const uint64_t NC = L ? in->n_changes : 0;
+    const uint64_t NI = NC ? in->n_input_ops : 0;
+    if (NI && (!in->action || !in->mark_type || !in->index || !in->count || !in->payload)) return fail(ctx, PTX_ERR_INVALID_ARG, "ptx_change: an InputOperation column is NULL");
+    PTX_HIP(ctx, ptx_enter(ctx));
+
+    /* work block: err | lds_need | rows [L] | list_words [L] | out_off [L + 1] | list_off [L + 1] */
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t rows_at = 16, lw_at = rows_at + a16((uint64_t)L * 4), oo_at = lw_at + a16((uint64_t)L * 4), lo_at = oo_at + a16(((uint64_t)L + 1) * 8), wbytes = lo_at + a16(((uint64_t)L + 1) * 8);
+    uint8_t* d_work = nullptr;
+    ptx_dbatch* cap = new ptx_dbatch(); /* the kernel's capacity-layout output, owned here */
+    ptx_dbatch* b = nullptr;
+    uint32_t *d_list = nullptr, *d_outw = nullptr;
+    auto drop = [&]() {
+        ptx_batch_free(ctx, cap);
+        cap = nullptr;
+        (void)ptx_dev_free(d_work);
+        (void)ptx_dev_free(d_list);
+        (void)ptx_dev_free(d_outw);
+        d_work = nullptr;
+        d_list = d_outw = nullptr;
+    };
+#define PTX_TRYD(call)                                  \
+    do {                                                \
+        hipError_t _e = (call);                         \
+        if (_e != hipSuccess) {                         \
+            std::string msg = std::string(#call) + ": " + hipGetErrorString(_e); \
+            drop();                                     \
+            ptx_batch_free(ctx, b);                     \
+            return fail(ctx, _e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, msg); \
+        }                                               \
+    } while (0)
+    if (ctx->up_h_cap < 64) { /* the small blocks that come down land in the context's pinned staging */
+        if (ctx->up_h) (void)hipHostFree(ctx->up_h);
+        ctx->up_h = nullptr;
+        ctx->up_h_cap = 0;
+        PTX_TRYD(hipHostMalloc((void**)&ctx->up_h, 4096, hipHostMallocDefault));
+        ctx->up_h_cap = 4096;
+    }
+    uint64_t* down = (uint64_t*)ctx->up_h; /* [0] err, [1] lds_need, [2] total rows, [3] total list words; later [0] rows made, [1] changes made, [2] the wide flag */
+    PTX_TRYD(ptx_dev_malloc((void**)&d_work, wbytes));
+    uint32_t* d_rows_need = (uint32_t*)(d_work + rows_at);
+    uint32_t* d_list_words = (uint32_t*)(d_work + lw_at);
+    uint64_t* d_out_off = (uint64_t*)(d_work + oo_at);
+    uint64_t* d_list_off = (uint64_t*)(d_work + lo_at);
+    uint64_t T = 0, list_total = 0, need = 4096;
+    if (L) {
+        PTX_TRYD(hipMemsetAsync(d_work, 0xFF, 8, ctx->stream));
+        PTX_TRYD(hipMemsetAsync(d_work + 8, 0, 8, ctx->stream));
+        PtxChangePrepArgs P;
+        memset(&P, 0, sizeof(P));
+        P.chg_off = in->chg_off;
+        P.op_off = in->op_off;
+        P.action = in->action;
+        P.count = in->count;
+        P.payload = in->payload;
+        P.n_changes = in->n_changes;
+        P.n_input_ops = in->n_input_ops;
+        P.n_values = in->n_values;
+        P.has_values = in->values ? 1u : 0u;
+        P.n_logs = L;
+        P.log_off = base->log_off;
+        P.log_hdr = base->log_hdr;
+        P.max_actors = na;
+        P.all_in_hbm = getenv("PTX_CHANGE_LIST_IN_HBM") != nullptr ? 1u : 0u; /* (tests: the list of EVERY log in global scratch) */
+        P.max_lds = ctx->max_lds;
+        P.rows = d_rows_need;
+        P.list_words = d_list_words;
+        P.err = (unsigned long long*)d_work;
+        P.lds_need = (unsigned long long*)(d_work + 8);
+        const uint64_t entries = ptx_change_offsets_entries(P);
+        hipLaunchKernelGGL(ptx_change_offsets_check_kernel, dim3((uint32_t)((entries + 255) / 256)), dim3(256), 0, ctx->stream, P);
+        hipLaunchKernelGGL(ptx_change_prep_kernel, dim3(L), dim3(64), 0, ctx->stream, P);
+        hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_rows_need, 0xFFFFFFFFu, d_out_off, L);
+        hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_list_words, 0xFFFFFFFFu, d_list_off, L);
+        PTX_TRYD(hipGetLastError());
+        PTX_TRYD(hipMemcpyAsync(down, d_work, 16, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipMemcpyAsync(down + 2, d_out_off + L, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipMemcpyAsync(down + 3, d_list_off + L, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipStreamSynchronize(ctx->stream)); /* the verdict: before any output is allocated */
+        const uint64_t err = down[0];
+        if (err != PTX_CP_NO_ERROR) {
+            const uint32_t code = (uint32_t)(err >> 56);
+            const unsigned long long at = err & PTX_CP_AT_MASK;
+            drop();
+            std::string msg;
+            if (code == PTX_CP_CHG_START) msg = "ptx_change: chg_off must start at 0";
+            else if (code == PTX_CP_CHG_ORDER) msg = "ptx_change: chg_off decreases at entry " + std::to_string(at);
+            else if (code == PTX_CP_OP_START) msg = "ptx_change: op_off must start at 0";
+            else if (code == PTX_CP_OP_ORDER) msg = "ptx_change: op_off decreases at entry " + std::to_string(at);
+            else if (code == PTX_CP_SIZES) msg = std::string("ptx_change: ") + (at ? "op_off" : "chg_off") + " does not end at the size the InputOperations were wrapped with";
+            else if (code == PTX_CP_VALUES) msg = "ptx_change: an insert points outside `values` (log " + std::to_string(at) + ")";
+            else msg = "ptx_change: more than 65534 ops for one log (log " + std::to_string(at) + ")";
+            return fail(ctx, PTX_ERR_INVALID_ARG, msg);
+        }
+        need = std::max<uint64_t>(need, down[1]);
+        T = down[2];
+        list_total = down[3];
+    }
+    const uint32_t lds_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, ctx->max_lds); /* larger logs report PTX_ERR_CAPACITY */
+
+    if (list_total) PTX_TRYD(dalloc(&d_list, list_total));
+    PTX_TRYD(dalloc(&d_outw, 3 * (uint64_t)L + 1));
+    uint32_t *d_status = d_outw, *d_rows = d_outw + L, *d_chgs = d_outw + 2 * (uint64_t)L, *d_wide = d_outw + 3 * (uint64_t)L;
+    PTX_TRYD(dalloc(&cap->op_id, T));
+    PTX_TRYD(dalloc(&cap->ref_a, T));
+    PTX_TRYD(dalloc(&cap->ref_b, T));
+    PTX_TRYD(dalloc(&cap->payload, T));
+    PTX_TRYD(dalloc(&cap->action, T));
+    PTX_TRYD(dalloc(&cap->mark_type, T));
+    PTX_TRYD(dalloc(&cap->side_a, T));
+    PTX_TRYD(dalloc(&cap->side_b, T));
+    PTX_TRYD(dalloc(&cap->chg_hdr, NC));
+    PTX_TRYD(dalloc(&cap->chg_env, NC * PTX_ENV_STRIDE(na)));
+    PTX_TRYD(dalloc(&cap->chg_env_hi, NC * PTX_ENV_STRIDE(na) + 2));
+    PTX_TRYD(hipMemsetAsync(d_wide, 0, 4, ctx->stream));
+    b = new ptx_dbatch();
+    b->n_logs = L;
+    b->max_actors = na;
+    PTX_TRYD(dalloc(&b->log_off, (uint64_t)L + 1));
+    PTX_TRYD(dalloc(&b->chg_off, (uint64_t)L + 1));
+    uint32_t any_wide = 0;
+    if (L) {
+        PtxChangeArgs A;
+        memset(&A, 0, sizeof(A));
+        A.log_off = base->log_off;
+        A.op_id = base->op_id;
+        A.ref_a = base->ref_a;
+        A.ref_b = base->ref_b;
+        A.action = base->action;
+        A.mark_type = base->mark_type;
+        A.side_a = base->side_a;
+        A.side_b = base->side_b;
+        A.log_hdr = base->log_hdr;
+        A.res = merged->logs;
+        A.elem_rank = merged->rank;
+        A.refs = merged->refs;
+        A.refs_hi = merged->refs_hi;
+        A.list_scratch = d_list;
+        A.list_off = d_list ? d_list_off : nullptr;
+        A.chg_off = base->chg_off;
+        A.chg_hdr = base->chg_hdr;
+        A.max_actors = na;
+        A.in_chg_off = in->chg_off;
+        A.in_op_off = in->op_off;
+        A.in_action = in->action;
+        A.in_mark_type = in->mark_type;
+        A.in_index = in->index;
+        A.in_count = in->count;
+        A.in_payload = in->payload;
+        A.in_values = in->values;
+        A.actor = in->actor;
+        A.out_off = d_out_off;
+        A.o_op_id = cap->op_id;
+        A.o_ref_a = cap->ref_a;
+        A.o_ref_b = cap->ref_b;
+        A.o_payload = cap->payload;
+        A.o_action = cap->action;
+        A.o_mark_type = cap->mark_type;
+        A.o_side_a = cap->side_a;
+        A.o_side_b = cap->side_b;
+        A.o_chg_hdr = cap->chg_hdr;
+        A.o_chg_env = cap->chg_env;
+        A.o_chg_env_hi = cap->chg_env_hi;
+        A.any_wide = d_wide;
+        A.status = d_status;
+        A.rows_made = d_rows;
+        A.chgs_made = d_chgs;
+        A.n_logs = L;
+        A.lds_bytes = lds_bytes;
+        hipLaunchKernelGGL(ptx_change_kernel, dim3(L), dim3(64), lds_bytes, ctx->stream, A);
+        /* the offsets of the made batch: failed logs contribute nothing */
+        hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_rows, 0xFFFFFFFFu, b->log_off, L);
+        hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_chgs, 0xFFFFFFFFu, b->chg_off, L);
+        PTX_TRYD(hipGetLastError());
+        PTX_TRYD(hipMemcpyAsync(status_out, d_status, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipMemcpyAsync(down, b->log_off + L, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipMemcpyAsync(down + 1, b->chg_off + L, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipMemcpyAsync(down + 2, d_wide, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PTX_TRYD(hipStreamSynchronize(ctx->stream));
+        b->n_ops = down[0];
+        b->n_changes = down[1];
+        any_wide = (uint32_t)down[2];
+    } else {
+        PTX_TRYD(hipMemsetAsync(b->log_off, 0, 8, ctx->stream));
+        PTX_TRYD(hipMemsetAsync(b->chg_off, 0, 8, ctx->stream));
+    }
+    PTX_TRYD(dalloc(&b->op_id, b->n_ops));
+    PTX_TRYD(dalloc(&b->ref_a, b->n_ops));
+    PTX_TRYD(dalloc(&b->ref_b, b->n_ops));
+    PTX_TRYD(dalloc(&b->payload, b->n_ops));
+    PTX_TRYD(dalloc(&b->action, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYD(dalloc(&b->mark_type, b->n_ops + PTX_BYTE_PAD));
+    PTX_TRYD(dalloc(&b->side_a, b->n_ops));
+    PTX_TRYD(dalloc(&b->side_b, b->n_ops));
+    PTX_TRYD(dalloc(&b->log_hdr, (uint64_t)L));
+    PTX_TRYD(dalloc(&b->chg_hdr, b->n_changes + PTX_ENV_PAD));
+    PTX_TRYD(dalloc(&b->chg_env, (b->n_changes + PTX_ENV_PAD) * PTX_ENV_STRIDE(na)));
+    if (any_wide) PTX_TRYD(dalloc(&b->chg_env_hi, (b->n_changes + PTX_ENV_PAD) * PTX_ENV_STRIDE(na))); /* some new seq / dep is beyond 16 bits */
+    if (L) {
+        PtxAppendCols S = {cap->op_id, cap->ref_a, cap->ref_b, cap->payload, cap->action, cap->mark_type, cap->side_a, cap->side_b,
+                           cap->chg_hdr, cap->chg_env, cap->chg_env_hi};
+        PtxAppendDst D = {b->op_id, b->ref_a, b->ref_b, b->payload, b->action, b->mark_type, b->side_a, b->side_b, b->chg_hdr, b->chg_env, b->chg_env_hi};
+        hipLaunchKernelGGL(ptx_take_rows_kernel, dim3(L), dim3(64), 0, ctx->stream, S, d_out_off, in->chg_off, d_rows, d_chgs, D, b->log_off, b->chg_off, na);
+        PTX_TRYD(hipGetLastError());
+        PTX_TRYD(hipStreamSynchronize(ctx->stream));
+    }
+#undef PTX_TRYD
     drop();
     const ptx_status st = census_and_shape(ctx, b, false);
     if (st != PTX_OK) {

@@ -173,6 +173,26 @@ class TextView:
         finally:
             eng.lib.ptx_replace_plan_free(C.byref(m))
 
+    def replace_plan_device(self, pattern, replacement_ids, n_batch_logs, actor, max_actors, ascii_nocase=False):
+        """replace_plan with the InputOperations left on the device (ptx_view_replace_plan_device): (wire.ReplacePlan with the per-log counts and ops=None, handle
+        of the resident ops — made for Engine.change_device, freed with Engine.free_input_ops).  actor[l] = actorRank of the replica behind log l of the batch."""
+        eng, pat = self.engine, self._pattern(pattern)
+        ids = np.ascontiguousarray(replacement_ids, dtype=np.uint32)
+        act = None if actor is None else np.ascontiguousarray(actor, dtype=np.uint32)
+        if act is not None and len(act) != n_batch_logs:
+            raise ValueError("actor must name every log of the batch")
+        m, h = abi.ptx_replace_plan(), C.c_void_p()
+        eng._check(eng.lib.ptx_view_replace_plan_device(eng.ctx, self.handle, pat.ctypes.data_as(abi.u16p), len(pat), abi.FIND_ASCII_NOCASE if ascii_nocase else 0,
+                                                        ids.ctypes.data_as(abi.u32p) if len(ids) else C.cast(None, abi.u32p), len(ids), n_batch_logs,
+                                                        act.ctypes.data_as(abi.u32p) if act is not None and len(act) else C.cast(None, abi.u32p), max_actors, C.byref(m), C.byref(h)))
+        try:
+            n, arr = int(m.n_logs), _copied
+            return wire.ReplacePlan(status=arr(m.status, np.uint32, n), n_matches=arr(m.n_matches, np.uint32, n), n_chosen=arr(m.n_chosen, np.uint32, n),
+                                    n_replaced=arr(m.n_replaced, np.uint32, n), ops=None, first_log=self.info()["first_log"], n_pattern=int(m.n_pattern),
+                                    n_replacement=int(m.n_replacement), kernel_ms=float(m.kernel_ms)), h
+        finally:
+            eng.lib.ptx_replace_plan_free(C.byref(m))
+
     def free(self):
         if self.handle is not None:
             self.engine.lib.ptx_text_view_free(self.engine.ctx, self.handle)
@@ -287,6 +307,82 @@ class Engine:
         h = C.c_void_p()
         self._check(self.lib.ptx_change(self.ctx, dbatch, dresult, C.byref(s), C.byref(h), status.ctypes.data_as(abi.u32p)))
         return h, status[: s.n_logs]
+
+    @staticmethod
+    def _input_ops_struct(ops):
+        s = abi.ptx_input_ops()
+        s.n_logs, s.max_actors = len(ops.chg_off) - 1, ops.max_actors
+        p = lambda a, t: a.ctypes.data_as(t) if a is not None else C.cast(None, t)  # noqa: E731
+        s.chg_off, s.op_off = p(ops.chg_off, abi.u64p), p(ops.op_off, abi.u64p)
+        s.action, s.mark_type = p(ops.action, abi.u8p), p(ops.mark_type, abi.u8p)
+        s.index, s.count, s.payload = p(ops.index, abi.u32p), p(ops.count, abi.u32p), p(ops.payload, abi.u32p)
+        s.values, s.n_values, s.actor = p(ops.values, abi.u32p), 0 if ops.values is None else len(ops.values), p(ops.actor, abi.u32p)
+        return s
+
+    def upload_input_ops(self, ops):
+        """wire.InputOps made resident (ptx_input_ops_upload): a handle for change_device, freed with free_input_ops.  Only the sizes are read here; what
+        Engine.change checks of the arrays on the host, change_device checks on the device."""
+        s, h = self._input_ops_struct(ops), C.c_void_p()
+        self._check(self.lib.ptx_input_ops_upload(self.ctx, C.byref(s), C.byref(h)))
+        return h
+
+    def wrap_input_ops(self, n_logs, n_changes, n_input_ops, n_values, max_actors, ptrs):
+        """Adopt caller-owned DEVICE columns as InputOperations (ptx_input_ops_wrap_device): `ptrs` maps the nine array names of ptx_input_ops (chg_off, op_off,
+        action, mark_type, index, count, payload, values, actor) to device addresses, e.g. torch tensors' data_ptr(); a missing name is NULL.  Nothing is
+        copied: the memory must outlive the handle and every call that takes it."""
+        s = abi.ptx_input_ops()
+        s.n_logs, s.max_actors, s.n_values = n_logs, max_actors, n_values
+        for name, typ in (("chg_off", abi.u64p), ("op_off", abi.u64p), ("action", abi.u8p), ("mark_type", abi.u8p), ("index", abi.u32p), ("count", abi.u32p),
+                          ("payload", abi.u32p), ("values", abi.u32p), ("actor", abi.u32p)):
+            setattr(s, name, C.cast(C.c_void_p(int(ptrs.get(name) or 0) or None), typ))
+        h = C.c_void_p()
+        self._check(self.lib.ptx_input_ops_wrap_device(self.ctx, C.byref(s), n_changes, n_input_ops, C.byref(h)))
+        return h
+
+    def download_input_ops(self, h):
+        """Resident InputOperations back on the host (ptx_input_ops_download): wire.InputOps."""
+        m = abi.ptx_host_input_ops()
+        self._check(self.lib.ptx_input_ops_download(self.ctx, h, C.byref(m)))
+        try:
+            o, arr, nl, nc, ni = m.ops, _copied, int(m.ops.n_logs), int(m.n_changes), int(m.n_input_ops)
+            return wire.InputOps(arr(o.chg_off, np.uint64, nl + 1 if o.chg_off else 0), arr(o.op_off, np.uint64, nc + 1 if o.op_off else 0), arr(o.action, np.uint8, ni),
+                                 arr(o.mark_type, np.uint8, ni), arr(o.index, np.uint32, ni), arr(o.count, np.uint32, ni), arr(o.payload, np.uint32, ni),
+                                 arr(o.values, np.uint32, int(o.n_values) if o.values else 0), arr(o.actor, np.uint32, nl), int(o.max_actors))
+        finally:
+            self.lib.ptx_host_input_ops_free(C.byref(m))
+
+    def free_input_ops(self, h):
+        self.lib.ptx_input_ops_free(self.ctx, h)
+
+    def change_device(self, dbatch, dresult, h):
+        """Engine.change for InputOperations that are resident (ptx_change_device): the same Changes and the same status; the rows every log makes, the checks
+        of the arrays and the launch's size are worked out on the device.  Returns (resident batch of the new Changes only, status per log)."""
+        n = int(self.lib.ptx_batch_n_logs(dbatch))
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        made = C.c_void_p()
+        self._check(self.lib.ptx_change_device(self.ctx, dbatch, dresult, h, C.byref(made), status.ctypes.data_as(abi.u32p)))
+        return made, status[:n]
+
+    def replace_text_resident(self, dbatch, dresult, view, batch, pattern, replacement_values, actors, ascii_nocase=False):
+        """replace_text without the InputOperations leaving the device: TextView.replace_plan_device and change_device.  The same arguments and the same return,
+        the wire.ReplacePlan carrying the per-log counts and no ops."""
+        value_ix = {v: i for i, v in enumerate(batch.values)}
+        ids = []
+        for v in replacement_values:
+            if not isinstance(v, str):
+                raise ValueError("Expected value inserted into text to be a string")
+            if v not in value_ix:
+                value_ix[v] = len(batch.values)
+                batch.values.append(v)
+            ids.append(value_ix[v])
+        actor = np.asarray([batch.doc_actors[batch.log_doc[l]].index(actors[l]) for l in range(batch.n_logs)], dtype=np.uint32)
+        max_actors = max(batch.max_actors, max((len(a) for a in batch.doc_actors), default=1))
+        plan, h = view.replace_plan_device(pattern, ids, batch.n_logs, actor, max_actors, ascii_nocase=ascii_nocase)
+        try:
+            made, status = self.change_device(dbatch, dresult, h)
+        finally:
+            self.free_input_ops(h)
+        return made, status, plan
 
     def replace_text(self, dbatch, dresult, view, batch, pattern, replacement_values, actors, ascii_nocase=False):
         """Replace all on many replicas at once: TextView.replace_plan of `view` (a view of `dresult` = merge of `dbatch`, WITH elem_rank) made into Changes by
