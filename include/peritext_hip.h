@@ -767,7 +767,9 @@ void ptx_slices_free(ptx_slices* m);
  *                      184 MB of text + 367 MB of prefix
  *   lifetimes          once ptx_text_view_create has returned the view reads nothing of `b` or `s`: `s` may be freed.  It reads the span rows of `r` — and
  *                      nothing else of it: a log's n_visible is taken from the view's own prefix — in slice and snippet calls: `r` must outlive the view
- *                      and stay the merge it was made from (a ptx_merge into `r` after an append makes the view stale: free it and make a new one)
+ *                      and stay the merge it was made from (a ptx_merge into `r` after an append makes the view stale: free it and make a new one).  The
+ *                      queries by format below (ptx_view_mark_runs, ptx_view_mark_snippets, ptx_view_find_in_marks) read the span rows too, and for
+ *                      PTX_MARK_COMMENT additionally the result's per-log n_cintervals and its cintervals rows
  *   ptx_view_find_text / ptx_view_text_slices   every field of ptx_matches / ptx_slices equals what ptx_result_find_text / ptx_result_text_slices return for the
  *                      same (b, r, s, range) — kernel_ms excepted —, the argument errors are the same, plus PTX_ERR_INVALID_ARG for a NULL view.  No text pass
  *                      and no prefix pass runs
@@ -820,6 +822,86 @@ ptx_status ptx_view_text_slices(ptx_ctx* ctx, const ptx_dview* v, const uint64_t
 ptx_status ptx_view_find_snippets(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log,
                                   uint32_t before, uint32_t after, ptx_snippets* out);
 void ptx_snippets_free(ptx_snippets* m);
+
+/* ---- a resident text view queried by FORMAT: the runs of a mark, their text, a find inside them ----
+ * "List every comment with the text it is anchored to", "every link and its text", "where is the bold text", "find this word, but only inside links".  The span
+ * rows and comment intervals of the merge are on the device; the runs are chosen there and never come down before the slice passes or the hit filter read them.
+ * A selector is (mark_type, id), mark_type one of PTX_MARK_*:
+ *   PTX_MARK_STRONG / PTX_MARK_EM   id must be PTX_MARK_ANY_ID.  A span row matches iff its attr has the flag.  A run is a MAXIMAL sequence of consecutive matching
+ *                      span rows of the log — two adjacent rows may both be strong and differ only in em —: [start of its first row, start of the row behind its
+ *                      last row), the log's n_visible behind the last row (taken from the view's own prefix).  run_id is 0
+ *   PTX_MARK_LINK      a row matches iff PTX_ATTR_LINK is set and (id == PTX_MARK_ANY_ID or (attr & PTX_ATTR_ID_MASK) == id).  A run also ends where the url id
+ *                      changes: two adjacent links to different urls are two runs.  run_id is the url id.  An id > PTX_ATTR_ID_MASK that is not
+ *                      PTX_MARK_ANY_ID is PTX_ERR_INVALID_ARG
+ *   PTX_MARK_COMMENT   the runs are the log's cintervals rows whose id equals `id`, with PTX_MARK_ANY_ID all of them, in the RESULT'S OWN ORDER (id, start) — which
+ *                      is NOT ascending start across ids: the intervals of one id ascend, those of the next id start over.  run_id is the doc-local comment id.
+ *                      A span with PTX_ATTR_COMMENT and no covering interval (`comment: []`) belongs to no run
+ *   order and cap      the runs of strong, em and link ascend by start within a log.  The listed runs are the FIRST max_runs_per_log of the log; n_runs counts
+ *                      ALL of them; max_runs_per_log == 0 is the count-only answer
+ *   units              run_unit = pre[run_start], run_len = pre[run_end] - pre[run_start] (pre: the view's element prefix).  A run made only of empty-string
+ *                      elements has run_len == 0 and is still a run
+ *   per-log status     exactly ptx_matches.status of the view.  Only a log that is PTX_OK has runs
+ *   ptx_view_mark_snippets   ONE slice per listed run, in run order, without the runs leaving the device in between: n_slices == run_off[n_logs].  The slice of run
+ *                      k is [run_start[k] - before, run_end[k] + after), saturating and clamped exactly as ptx_view_find_snippets windows a hit; the slice
+ *                      fields are those of ptx_snippets.  match_unit[k] = pre[run_start[k]] - pre[elem_start[k]]: where the run begins inside the snippet's
+ *                      text.  With before == after == 0 the snippet IS the run's text — the text each comment is anchored to
+ *   ptx_view_find_in_marks   the hits of ptx_view_find_text with max_hits_per_log = 0xFFFFFFFF whose [hit_start, hit_end) lies inside ONE run of the selector:
+ *                      run_start <= hit_start && hit_end <= run_end.  Containment is over ELEMENTS, because marks are per element: it is the range addMark
+ *                      {startIndex: hit_start, endIndex: hit_end} would take.  n_matches counts the contained hits, the listed ones are the first
+ *                      max_hits_per_log of them; order and every other field as ptx_view_find_text.  PTX_MARK_COMMENT needs a specific id: PTX_MARK_ANY_ID
+ *                      there is PTX_ERR_INVALID_ARG, because a log's intervals of different ids are not sorted by start.  More than 2^32 - 1 matches in the view
+ *                      is PTX_ERR_CAPACITY, as for find
+ *   lifetimes          as for the view's other queries: `r` must outlive the view and stay the merge it was made from.  These calls read its span rows; comment
+ *                      queries additionally read its per-log n_cintervals and its cintervals rows
+ * PTX_ERR_INVALID_ARG: a NULL view, an unknown mark_type, the id errors above, and for ptx_view_find_in_marks the argument errors of ptx_view_find_text.  An empty
+ * view returns the empty result (run_off = {0}).  elem_rank is not needed (PTX_FLAG_NO_ELEM_RANK contexts work).  Every call synchronises. */
+#define PTX_MARK_ANY_ID 0xFFFFFFFFu
+typedef struct ptx_mark_runs {
+    uint32_t n_logs;
+    uint32_t mark_type;
+    float kernel_ms;               /* HIP events around every launch of the call */
+    uint32_t reserved;
+    const uint32_t* status;        /* [n_logs] as ptx_matches */
+    const uint32_t* n_runs;        /* [n_logs] ALL runs of the log, listed or not */
+    const uint64_t* run_off;       /* [n_logs + 1] listed runs: min(n_runs[l], max_runs_per_log) per log */
+    const uint32_t* run_start;     /* [run_off[n_logs]] visible index of the run's first element */
+    const uint32_t* run_end;       /* ... of its last element, + 1 */
+    const uint32_t* run_id;        /* ... 0 (strong, em), the url id (link), the doc-local comment id (comment) */
+    const uint32_t* run_unit;      /* ... code-unit offset of the run within the log's text */
+    const uint32_t* run_len;       /* ... its length in code units */
+    void* owner;
+} ptx_mark_runs;
+typedef struct ptx_mark_snippets {
+    uint32_t n_logs;
+    uint32_t mark_type;
+    float kernel_ms;
+    uint32_t n_slices;             /* == run_off[n_logs] */
+    const uint32_t* status;
+    const uint32_t* n_runs;
+    const uint64_t* run_off;
+    const uint32_t* run_start;
+    const uint32_t* run_end;
+    const uint32_t* run_id;
+    const uint32_t* run_unit;
+    const uint32_t* run_len;
+    const uint32_t* elem_start;    /* [n_slices] as ptx_snippets, of the slice [run_start - before, run_end + after) */
+    const uint32_t* elem_end;
+    const uint64_t* unit_off;      /* [n_slices + 1] */
+    const uint16_t* text;          /* [unit_off[n_slices]] */
+    const uint64_t* sspan_off;     /* [n_slices + 1] */
+    const ptx_span* sspans;        /* [sspan_off[n_slices]] */
+    const uint32_t* sspan_unit;
+    const uint32_t* match_unit;    /* [n_slices] code-unit offset of the run's first unit within the snippet's text */
+    void* owner;
+} ptx_mark_snippets;
+/* Owned by the library until ptx_mark_runs_free / ptx_mark_snippets_free / ptx_matches_free. */
+ptx_status ptx_view_mark_runs(ptx_ctx* ctx, const ptx_dview* v, uint32_t mark_type, uint32_t id, uint32_t max_runs_per_log, ptx_mark_runs* out);
+void ptx_mark_runs_free(ptx_mark_runs* m);
+ptx_status ptx_view_mark_snippets(ptx_ctx* ctx, const ptx_dview* v, uint32_t mark_type, uint32_t id, uint32_t max_runs_per_log, uint32_t before, uint32_t after,
+                                  ptx_mark_snippets* out);
+void ptx_mark_snippets_free(ptx_mark_snippets* m);
+ptx_status ptx_view_find_in_marks(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t mark_type, uint32_t id,
+                                  uint32_t max_hits_per_log, ptx_matches* out);
 
 /* ---- find and replace on a resident text view: hits into change() input ----
  * The reference's editor turns a ProseMirror ReplaceStep into a `delete` followed by an `insert` at the same index (bridge.ts:425-446).  This answers, for every

@@ -364,8 +364,58 @@ class ptx_snippets(C.Structure):
     ]
 
 
+# queries by format on a view (ptx_view_mark_runs, ptx_view_mark_snippets, ptx_view_find_in_marks; peritext_amd/csrc/markrun_core.h)
+MARK_STRONG, MARK_EM, MARK_COMMENT, MARK_LINK = 0, 1, 2, 3  # PTX_MARK_*
+MARK_ANY_ID = 0xFFFFFFFF  # PTX_MARK_ANY_ID
+MARKRUN_STEP = 64  # span or cinterval rows, and hits of the filter, per step of a wave's walk
+
+
+class ptx_mark_runs(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("mark_type", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("reserved", C.c_uint32),
+        ("status", u32p),
+        ("n_runs", u32p),
+        ("run_off", u64p),
+        ("run_start", u32p),
+        ("run_end", u32p),
+        ("run_id", u32p),
+        ("run_unit", u32p),
+        ("run_len", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
+class ptx_mark_snippets(C.Structure):
+    _fields_ = [
+        ("n_logs", C.c_uint32),
+        ("mark_type", C.c_uint32),
+        ("kernel_ms", C.c_float),
+        ("n_slices", C.c_uint32),
+        ("status", u32p),
+        ("n_runs", u32p),
+        ("run_off", u64p),
+        ("run_start", u32p),
+        ("run_end", u32p),
+        ("run_id", u32p),
+        ("run_unit", u32p),
+        ("run_len", u32p),
+        ("elem_start", u32p),
+        ("elem_end", u32p),
+        ("unit_off", u64p),
+        ("text", u16p),
+        ("sspan_off", u64p),
+        ("sspans", C.c_void_p),
+        ("sspan_unit", u32p),
+        ("match_unit", u32p),
+        ("owner", C.c_void_p),
+    ]
+
+
 # find and replace on a view (ptx_view_replace_plan; peritext_amd/csrc/replace_core.h)
-REPLACE_TILE = 64  # PTX_REPLACE_TILE: hits per step of the select walk
+REPLACE_TILE = 64 # PTX_REPLACE_TILE: hits per step of the select walk
 CHANGE_ROWS_MAX = 65534  # PTX_CHANGE_ROWS_MAX: rows the Changes of one log may make in one ptx_change call
 
 
@@ -486,6 +536,11 @@ FUNCTIONS = {
     "ptx_view_text_slices": (C.c_int32, [vp, vp, u64p, u32p, u32p, C.POINTER(ptx_slices)]),
     "ptx_view_find_snippets": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_snippets)]),
     "ptx_snippets_free": (None, [C.POINTER(ptx_snippets)]),
+    "ptx_view_mark_runs": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_mark_runs)]),
+    "ptx_mark_runs_free": (None, [C.POINTER(ptx_mark_runs)]),
+    "ptx_view_mark_snippets": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_mark_snippets)]),
+    "ptx_mark_snippets_free": (None, [C.POINTER(ptx_mark_snippets)]),
+    "ptx_view_find_in_marks": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ptx_matches)]),
     "ptx_view_replace_plan": (C.c_int32, [vp, vp, u16p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.POINTER(ptx_replace_plan)]),
     "ptx_replace_plan_free": (None, [C.POINTER(ptx_replace_plan)]),
     "ptx_input_ops_upload": (C.c_int32, [vp, C.POINTER(ptx_input_ops), C.POINTER(vp)]),

@@ -43,6 +43,7 @@
 #include "slice_core.h"
 #include "view_core.h"
 #include "replace_core.h"
+#include "markrun_core.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 /* kernels                                                                                          */
@@ -703,6 +704,26 @@ extern "C" __global__ void __launch_bounds__(64) ptx_replace_select_kernel(PtxRe
 extern "C" __global__ void __launch_bounds__(256) ptx_replace_emit_kernel(PtxReplaceArgs A) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k < A.V.n_hits) ptx_replace_emit_one(A, k); /* (the grid is ceil(n_hits / 256) <= 2^24 blocks: k does not wrap) */
+}
+
+/* ---- queries by format on a view (markrun_core.h): one wave per log counts the runs of the selector, ptx_text_offsets_kernel scans min(count, cap), one wave per
+ *      log lists its first runs, a lane per listed run measures it (and writes the snippet window); for a find inside marks one wave per log counts the hits its
+ *      uncapped runs contain, ptx_find_offsets_kernel scans them under the cap, and the same walk compacts them ---- */
+extern "C" __global__ void __launch_bounds__(64) ptx_markrun_count_kernel(PtxMarkRunArgs A) {
+    if (blockIdx.x < A.n_logs) ptx_markrun_count_log<64>(A, blockIdx.x);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_markrun_emit_kernel(PtxMarkRunArgs A) {
+    if (blockIdx.x < A.n_logs) ptx_markrun_emit_log<64>(A, blockIdx.x);
+}
+extern "C" __global__ void __launch_bounds__(256) ptx_markrun_finish_kernel(PtxMarkRunArgs A) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < A.n_listed) ptx_markrun_finish_one(A, k); /* (the grid is ceil(n_listed / 256) <= 2^24 blocks: k does not wrap) */
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_markrun_filter_count_kernel(PtxMarkFilterArgs A) {
+    if (blockIdx.x < A.n_logs) ptx_markrun_filter_log<64, false>(A, blockIdx.x);
+}
+extern "C" __global__ void __launch_bounds__(64) ptx_markrun_filter_emit_kernel(PtxMarkFilterArgs A) {
+    if (blockIdx.x < A.n_logs) ptx_markrun_filter_log<64, true>(A, blockIdx.x);
 }
 
 /* log_off of a tiled batch: copy k of log l starts at k * n_ops + log_off[l] */
@@ -3430,6 +3451,410 @@ ptx_status ptx_view_text_slices(ptx_ctx* ctx, const ptx_dview* v, const uint64_t
     out->text = (const uint16_t*)hp1;
     out->sspans = (const ptx_span*)(hp1 + ot_bytes);
     out->sspan_unit = (const uint32_t*)(hp1 + ot_bytes + os_bytes);
+    out->owner = h;
+    return PTX_OK;
+}
+
+/* ---- queries by format on a view (markrun_core.h): count -> scan -> the number of listed runs comes down -> emit -> finish (-> bounds -> scan -> the slice
+ *      passes).  ptx_view_mark_runs has two waits, ptx_view_mark_snippets three; ptx_view_find_in_marks keeps the uncapped runs on the device and runs the view's
+ *      hit passes and the filter over them: four waits (runs, hits, kept hits, the answer) ---- */
+struct ptx_host_mark_snippets {
+    ptx_host_result runs, cut;
+};
+
+void ptx_mark_runs_free(ptx_mark_runs* m) {
+    if (!m) return;
+    delete (ptx_host_result*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+void ptx_mark_snippets_free(ptx_mark_snippets* m) {
+    if (!m) return;
+    delete (ptx_host_mark_snippets*)m->owner;
+    memset(m, 0, sizeof(*m));
+}
+
+static ptx_status view_mark_check(ptx_ctx* ctx, uint32_t mark_type, uint32_t id, bool find) {
+    if (mark_type != PTX_MARK_STRONG && mark_type != PTX_MARK_EM && mark_type != PTX_MARK_COMMENT && mark_type != PTX_MARK_LINK)
+        return fail(ctx, PTX_ERR_INVALID_ARG, "unknown mark type");
+    if ((mark_type == PTX_MARK_STRONG || mark_type == PTX_MARK_EM) && id != PTX_MARK_ANY_ID) return fail(ctx, PTX_ERR_INVALID_ARG, "strong and em take PTX_MARK_ANY_ID");
+    if (mark_type == PTX_MARK_LINK && id != PTX_MARK_ANY_ID && id > PTX_ATTR_ID_MASK) return fail(ctx, PTX_ERR_INVALID_ARG, "url id beyond PTX_ATTR_ID_MASK");
+    if (find && mark_type == PTX_MARK_COMMENT && id == PTX_MARK_ANY_ID)
+        return fail(ctx, PTX_ERR_INVALID_ARG, "a find inside comments needs one comment id: intervals of different ids are not sorted by start");
+    return PTX_OK;
+}
+
+enum { PTX_MARKS_RUNS = 0, PTX_MARKS_SNIPPETS = 1, PTX_MARKS_DEVICE = 2 };
+/* PTX_MARKS_DEVICE: the listed runs stay where the passes left them; the caller gives both blocks back to the pool */
+struct ptx_mark_runs_keep {
+    uint8_t *d0 = nullptr, *d1 = nullptr;
+    const uint64_t* run_off = nullptr; /* device [n_logs + 1] */
+    const uint32_t *run_start = nullptr, *run_end = nullptr;
+    float ms = 0.f;
+};
+
+/* THE run sequence of all three entry points; the arguments are checked.  h->pinned[0]: status | n_runs | run_off,  h->pinned[1]: run_start | run_end | run_id |
+ * run_unit | run_len and, for snippets, | elem_start | elem_end | match_unit | unit_off, sspan_off;  cut->pinned[0]: text | sspans | sspan_unit */
+static ptx_status view_marks_impl(ptx_ctx* ctx, const ptx_dview* v, uint32_t mark_type, uint32_t id, uint32_t cap, int mode, uint32_t before, uint32_t after, ptx_host_result* h,
+                                  ptx_host_result* cut, ptx_mark_snippets* out, ptx_mark_runs_keep* keep) {
+    PTX_HIP(ctx, ptx_enter(ctx));
+    const bool snip = mode == PTX_MARKS_SNIPPETS, dev = mode == PTX_MARKS_DEVICE;
+    const uint32_t n_logs = v->n_logs;
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status (the host's only: the view keeps the device's) | n_runs | run_off (two rows: the scan kernel's) */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), ro_at = 2 * st_bytes, blk0 = ro_at + a16(2 * no * 8);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, blk0, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess && n_logs) e = ptx_dev_malloc((void**)&d0, blk0);
+    uint64_t* run_off = (uint64_t*)(hp0 + ro_at);
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t nr = 0, out_units = 0, out_rows = 0, ot_bytes = 0, os_bytes = 0;
+    bool too_many = false;
+    PtxMarkRunArgs A;
+    memset(&A, 0, sizeof(A));
+    if (e == hipSuccess) {
+        if (n_logs) memcpy(hp0, v->h_status.data(), (size_t)n_logs * 4);
+        run_off[0] = 0; /* an empty view: run_off = {0} */
+    }
+    if (e == hipSuccess && n_logs) {
+        A.log_off = v->log_off;
+        A.spans = v->r->spans;
+        A.cints = v->r->cints;
+        A.logs = v->r->logs;
+        A.status = v->status;
+        A.span_off = v->off + no;
+        A.pre_off = v->pre_off;
+        A.pre = v->pre;
+        A.first_log = v->first_log;
+        A.n_logs = n_logs;
+        A.mark_type = mark_type;
+        A.id = id;
+        A.cap = cap;
+        A.before = before;
+        A.after = after;
+        A.n_runs = (uint32_t*)(d0 + st_bytes);
+        A.run_off = (uint64_t*)(d0 + ro_at);
+        e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_markrun_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.run_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + st_bytes, d0 + st_bytes, st_bytes + no * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nr = run_off[n_logs];
+        if (e == hipSuccess && nr > 0xFFFFFFFFull) too_many = true, e = hipErrorInvalidValue; /* a lane per listed run, a slice per run */
+    }
+    /* block 1, device and pinned host alike: run_start | run_end | run_id | run_unit | run_len and, for snippets, | elem_start | elem_end | match_unit | unit_off,
+     * sspan_off — all of it comes down in one copy, nothing goes up —; the device's goes on with win_start | win_end | slice_log | first_span | src_off */
+    const uint64_t nso = nr + 1, col = a16(nr * 4), oo_at = (snip ? 8 : 5) * col, down1 = oo_at + (snip ? a16(2 * nso * 8) : 0), hblk1 = down1 + 16;
+    const uint64_t ws_at = down1, sl_at = ws_at + 2 * col, src_at = sl_at + 2 * col, dblk1 = snip ? src_at + a16(nr * 8) + 16 : hblk1;
+    if (e == hipSuccess && !dev) e = hipHostMalloc((void**)&hp1, hblk1, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    uint64_t* out_off = (uint64_t*)(hp1 + oo_at);
+    if (e == hipSuccess && snip) out_off[0] = out_off[nso] = 0; /* no runs: unit_off = sspan_off = {0} */
+    PtxSliceArgs S;
+    memset(&S, 0, sizeof(S));
+    if (e == hipSuccess && nr) {
+        e = ptx_dev_malloc((void**)&d1, dblk1);
+        if (e == hipSuccess) {
+            A.n_listed = (uint32_t)nr;
+            A.run_start = (uint32_t*)d1;
+            A.run_end = (uint32_t*)(d1 + col);
+            A.run_id = (uint32_t*)(d1 + 2 * col);
+            A.run_unit = (uint32_t*)(d1 + 3 * col);
+            A.run_len = (uint32_t*)(d1 + 4 * col);
+            if (snip) {
+                A.match_unit = (uint32_t*)(d1 + 7 * col);
+                A.win_start = (uint32_t*)(d1 + ws_at);
+                A.win_end = (uint32_t*)(d1 + ws_at + col);
+                view_text_args(v, S.T);
+                S.slice_off = A.run_off; /* one slice per listed run, in run order */
+                S.slice_start = A.win_start;
+                S.slice_end = A.win_end;
+                S.n_slices = (uint32_t)nr;
+                S.pre_off = v->pre_off;
+                S.pre = v->pre;
+                S.elem_start = (uint32_t*)(d1 + 5 * col);
+                S.elem_end = (uint32_t*)(d1 + 6 * col);
+                S.out_off = (uint64_t*)(d1 + oo_at);
+                S.slice_log = (uint32_t*)(d1 + sl_at);
+                S.first_span = (uint32_t*)(d1 + sl_at + col);
+                S.src_off = (uint64_t*)(d1 + src_at);
+            }
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            const uint32_t grid = (uint32_t)((nr + 255) / 256);
+            hipLaunchKernelGGL(ptx_markrun_emit_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, A);
+            if (!dev) hipLaunchKernelGGL(ptx_markrun_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream, A);
+            if (snip) {
+                hipLaunchKernelGGL(ptx_slice_bounds_kernel, dim3(grid), dim3(256), 0, ctx->stream, S);
+                hipLaunchKernelGGL(ptx_text_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, S.out_off, (uint32_t)nr);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess && !dev) e = hipMemcpyAsync(hp1, d1, snip ? oo_at + 2 * nso * 8 : 5 * col, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess && snip) {
+            out_units = out_off[nr];
+            out_rows = out_off[nso + nr];
+        }
+    }
+    if (e == hipSuccess && snip) e = slice_emit_passes(ctx, S, out_units, out_rows, cut, 0, &ot_bytes, &os_bytes, &ms[2]);
+    if (e != hipSuccess || !dev) {
+        (void)ptx_dev_free(d0);
+        (void)ptx_dev_free(d1);
+    }
+    if (e != hipSuccess) {
+        if (too_many) return fail(ctx, PTX_ERR_CAPACITY, "more than 2^32 - 1 listed runs: lower max_runs_per_log or the range");
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view marks: ") + hipGetErrorString(e));
+    }
+    if (dev) {
+        keep->d0 = d0;
+        keep->d1 = d1;
+        keep->run_off = A.run_off;
+        keep->run_start = A.run_start;
+        keep->run_end = A.run_end;
+        keep->ms = ms[0] + ms[1];
+        return PTX_OK;
+    }
+    out->n_logs = n_logs;
+    out->mark_type = mark_type;
+    out->kernel_ms = ms[0] + ms[1] + ms[2];
+    out->n_slices = snip ? (uint32_t)nr : 0u;
+    out->status = (const uint32_t*)hp0;
+    out->n_runs = (const uint32_t*)(hp0 + st_bytes);
+    out->run_off = run_off;
+    out->run_start = (const uint32_t*)hp1;
+    out->run_end = (const uint32_t*)(hp1 + col);
+    out->run_id = (const uint32_t*)(hp1 + 2 * col);
+    out->run_unit = (const uint32_t*)(hp1 + 3 * col);
+    out->run_len = (const uint32_t*)(hp1 + 4 * col);
+    if (snip) {
+        const uint8_t* hp2 = (const uint8_t*)cut->pinned[0];
+        out->elem_start = (const uint32_t*)(hp1 + 5 * col);
+        out->elem_end = (const uint32_t*)(hp1 + 6 * col);
+        out->match_unit = (const uint32_t*)(hp1 + 7 * col);
+        out->unit_off = out_off;
+        out->sspan_off = out_off + nso;
+        out->text = (const uint16_t*)hp2;
+        out->sspans = (const ptx_span*)(hp2 + ot_bytes);
+        out->sspan_unit = (const uint32_t*)(hp2 + ot_bytes + os_bytes);
+    }
+    return PTX_OK;
+}
+
+ptx_status ptx_view_mark_runs(ptx_ctx* ctx, const ptx_dview* v, uint32_t mark_type, uint32_t id, uint32_t max_runs_per_log, ptx_mark_runs* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_mark_check(ctx, mark_type, id, false);
+    if (st != PTX_OK) return st;
+    ptx_host_result* h = new ptx_host_result();
+    ptx_mark_snippets m;
+    memset(&m, 0, sizeof(m));
+    st = view_marks_impl(ctx, v, mark_type, id, max_runs_per_log, PTX_MARKS_RUNS, 0u, 0u, h, nullptr, &m, nullptr);
+    if (st != PTX_OK) {
+        delete h;
+        return st;
+    }
+    out->n_logs = m.n_logs;
+    out->mark_type = m.mark_type;
+    out->kernel_ms = m.kernel_ms;
+    out->status = m.status;
+    out->n_runs = m.n_runs;
+    out->run_off = m.run_off;
+    out->run_start = m.run_start;
+    out->run_end = m.run_end;
+    out->run_id = m.run_id;
+    out->run_unit = m.run_unit;
+    out->run_len = m.run_len;
+    out->owner = h;
+    return PTX_OK;
+}
+
+ptx_status ptx_view_mark_snippets(ptx_ctx* ctx, const ptx_dview* v, uint32_t mark_type, uint32_t id, uint32_t max_runs_per_log, uint32_t before, uint32_t after,
+                                  ptx_mark_snippets* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_mark_check(ctx, mark_type, id, false);
+    if (st != PTX_OK) return st;
+    ptx_host_mark_snippets* h = new ptx_host_mark_snippets();
+    st = view_marks_impl(ctx, v, mark_type, id, max_runs_per_log, PTX_MARKS_SNIPPETS, before, after, &h->runs, &h->cut, out, nullptr);
+    if (st != PTX_OK) {
+        delete h;
+        memset(out, 0, sizeof(*out));
+        return st;
+    }
+    out->owner = h;
+    return PTX_OK;
+}
+
+/* the view's hit passes, uncapped, into scratch; the filter over the runs `K` holds; the kept hits down.  h->pinned[0]: status | n_matches | hit_off,
+ * h->pinned[1]: hit_unit | hit_start | hit_end */
+static ptx_status view_find_in_marks_impl(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t max_hits_per_log,
+                                          const ptx_mark_runs_keep& K, ptx_host_result* h, ptx_matches* out) {
+    PTX_HIP(ctx, ptx_enter(ctx));
+    const uint32_t n_logs = v->n_logs;
+    const uint64_t no = (uint64_t)n_logs + 1;
+    auto a16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    /* block 0, device and pinned host alike: status (the host's only) | n_matches | hit_off — what comes down — | the pattern; the device's goes on with the
+     * uncapped counts and their offsets */
+    const uint64_t st_bytes = a16((uint64_t)n_logs * 4), down0 = 2 * st_bytes + a16(no * 8), pat_at = down0, hblk0 = pat_at + a16((uint64_t)n_pattern * 2);
+    const uint64_t na_at = hblk0, ao_at = na_at + st_bytes, dblk0 = ao_at + a16(no * 8);
+    uint8_t *hp0 = nullptr, *hp1 = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
+    hipError_t e = hipHostMalloc((void**)&hp0, hblk0 + 16, hipHostMallocDefault);
+    h->pinned[0] = hp0;
+    if (e == hipSuccess && n_logs) e = ptx_dev_malloc((void**)&d0, dblk0);
+    uint64_t* hit_off = (uint64_t*)(hp0 + 2 * st_bytes);
+    uint64_t* total = (uint64_t*)(hp0 + hblk0); /* the uncapped hits of the view */
+    float ms[3] = {0.f, 0.f, 0.f};
+    uint64_t nall = 0, nkept = 0;
+    bool too_many = false;
+    PtxViewArgs V;
+    PtxMarkFilterArgs F;
+    memset(&V, 0, sizeof(V));
+    memset(&F, 0, sizeof(F));
+    if (e == hipSuccess) {
+        if (n_logs) memcpy(hp0, v->h_status.data(), (size_t)n_logs * 4);
+        memcpy(hp0 + pat_at, pattern, (size_t)n_pattern * 2); /* the caller's pattern is free to go */
+        hit_off[0] = 0;                                       /* an empty view: hit_off = {0} */
+        *total = 0;
+    }
+    if (e == hipSuccess && n_logs) {
+        view_text_args(v, V.F.T);
+        V.F.n_matches = (uint32_t*)(d0 + na_at);
+        V.F.hit_off = (uint64_t*)(d0 + ao_at);
+        V.F.pattern = (const uint16_t*)(d0 + pat_at);
+        V.F.n_pattern = n_pattern;
+        V.F.flags = flags;
+        V.F.cap = 0xFFFFFFFFu;
+        V.pre_off = v->pre_off;
+        V.pre = v->pre;
+        e = hipMemcpyAsync(d0 + pat_at, hp0 + pat_at, (size_t)n_pattern * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_find_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, V.F);
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)V.F.n_matches, 0xFFFFFFFFu, V.F.hit_off, n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(total, V.F.hit_off + n_logs, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nall = *total;
+        if (e == hipSuccess && nall > 0xFFFFFFFFull) too_many = true, e = hipErrorInvalidValue; /* a lane per hit */
+    }
+    /* block 1, device only: hit_unit | hit_start | hit_end of ALL hits */
+    const uint64_t cola = a16(nall * 4);
+    if (e == hipSuccess && n_logs) {
+        if (nall) e = ptx_dev_malloc((void**)&d1, 3 * cola + 16);
+        if (e == hipSuccess) {
+            V.n_hits = (uint32_t)nall;
+            V.F.hit_unit = (uint32_t*)d1;
+            V.F.hit_start = (uint32_t*)(d1 + cola);
+            V.F.hit_end = (uint32_t*)(d1 + 2 * cola);
+            F.n_logs = n_logs;
+            F.cap = max_hits_per_log;
+            F.hit_off = V.F.hit_off;
+            F.hit_unit = V.F.hit_unit;
+            F.hit_start = V.F.hit_start;
+            F.hit_end = V.F.hit_end;
+            F.run_off = K.run_off;
+            F.run_start = K.run_start;
+            F.run_end = K.run_end;
+            F.n_kept = (uint32_t*)(d0 + st_bytes);
+            F.out_off = (const uint64_t*)(d0 + 2 * st_bytes);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            if (nall) {
+                hipLaunchKernelGGL(ptx_view_positions_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, V.F);
+                hipLaunchKernelGGL(ptx_view_locate_kernel, dim3((uint32_t)((nall + 255) / 256)), dim3(256), 0, ctx->stream, V);
+            }
+            hipLaunchKernelGGL(ptx_markrun_filter_count_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, F); /* (a view without a hit: zeros) */
+            hipLaunchKernelGGL(ptx_find_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)F.n_kept, max_hits_per_log, (uint64_t*)(d0 + 2 * st_bytes), n_logs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp0 + st_bytes, d0 + st_bytes, down0 - st_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], ctx->ev0, ctx->ev1);
+        if (e == hipSuccess) nkept = hit_off[n_logs];
+    }
+    /* block 2, device and pinned host alike: hit_unit | hit_start | hit_end of the listed kept hits */
+    const uint64_t col = a16(nkept * 4);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&hp1, 3 * col + 16, hipHostMallocDefault);
+    h->pinned[1] = hp1;
+    if (e == hipSuccess && nkept) {
+        e = ptx_dev_malloc((void**)&d2, 3 * col + 16);
+        if (e == hipSuccess) {
+            F.out_unit = (uint32_t*)d2;
+            F.out_start = (uint32_t*)(d2 + col);
+            F.out_end = (uint32_t*)(d2 + 2 * col);
+            e = hipEventRecord(ctx->ev0, ctx->stream);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ptx_markrun_filter_emit_kernel, dim3(n_logs), dim3(64), 0, ctx->stream, F);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp1, d2, 3 * col, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void)hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], ctx->ev0, ctx->ev1);
+    }
+    (void)ptx_dev_free(d0);
+    (void)ptx_dev_free(d1);
+    (void)ptx_dev_free(d2);
+    if (e != hipSuccess) {
+        if (too_many) return fail(ctx, PTX_ERR_CAPACITY, "more than 2^32 - 1 matches in the view: narrow the range");
+        return fail(ctx, e == hipErrorOutOfMemory ? PTX_ERR_OOM : PTX_ERR_HIP, std::string("view find in marks: ") + hipGetErrorString(e));
+    }
+    out->n_logs = n_logs;
+    out->n_pattern = n_pattern;
+    out->kernel_ms = K.ms + ms[0] + ms[1] + ms[2];
+    out->status = (const uint32_t*)hp0;
+    out->n_matches = (const uint32_t*)(hp0 + st_bytes);
+    out->hit_off = hit_off;
+    out->hit_unit = (const uint32_t*)hp1;
+    out->hit_start = (const uint32_t*)(hp1 + col);
+    out->hit_end = (const uint32_t*)(hp1 + 2 * col);
+    return PTX_OK;
+}
+
+ptx_status ptx_view_find_in_marks(ptx_ctx* ctx, const ptx_dview* v, const uint16_t* pattern, uint32_t n_pattern, uint32_t flags, uint32_t mark_type, uint32_t id,
+                                  uint32_t max_hits_per_log, ptx_matches* out) {
+    if (!ctx || !v || !out) return PTX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    ptx_status st = view_find_check(ctx, pattern, n_pattern, flags);
+    if (st == PTX_OK) st = view_mark_check(ctx, mark_type, id, true);
+    if (st != PTX_OK) return st;
+    ptx_mark_runs_keep K;
+    {
+        ptx_host_result tmp; /* the runs' counts: nobody asks for them */
+        st = view_marks_impl(ctx, v, mark_type, id, 0xFFFFFFFFu, PTX_MARKS_DEVICE, 0u, 0u, &tmp, nullptr, nullptr, &K);
+    }
+    if (st != PTX_OK) return st;
+    ptx_host_result* h = new ptx_host_result();
+    st = view_find_in_marks_impl(ctx, v, pattern, n_pattern, flags, max_hits_per_log, K, h, out);
+    (void)ptx_dev_free(K.d0);
+    (void)ptx_dev_free(K.d1);
+    if (st != PTX_OK) {
+        delete h;
+        memset(out, 0, sizeof(*out));
+        return st;
+    }
     out->owner = h;
     return PTX_OK;
 }

@@ -151,6 +151,53 @@ class TextView:
         finally:
             eng.lib.ptx_snippets_free(C.byref(m))
 
+    def mark_runs(self, mark_type, id=abi.MARK_ANY_ID, max_runs_per_log=0xFFFFFFFF):
+        """The runs of a mark, chosen on the device (ptx_view_mark_runs): maximal sequences of span rows with the strong / em flag or the same link url, or the
+        comment intervals of one id (abi.MARK_ANY_ID: any url, every comment): wire.MarkRuns."""
+        eng = self.engine
+        m = abi.ptx_mark_runs()
+        eng._check(eng.lib.ptx_view_mark_runs(eng.ctx, self.handle, mark_type, id, max_runs_per_log, C.byref(m)))
+        try:
+            n, arr = int(m.n_logs), _copied
+            run_off = arr(m.run_off, np.uint64, n + 1)
+            k = int(run_off[n])
+            return wire.MarkRuns(status=arr(m.status, np.uint32, n), n_runs=arr(m.n_runs, np.uint32, n), run_off=run_off, run_start=arr(m.run_start, np.uint32, k),
+                                 run_end=arr(m.run_end, np.uint32, k), run_id=arr(m.run_id, np.uint32, k), run_unit=arr(m.run_unit, np.uint32, k),
+                                 run_len=arr(m.run_len, np.uint32, k), mark_type=int(m.mark_type), kernel_ms=float(m.kernel_ms))
+        finally:
+            eng.lib.ptx_mark_runs_free(C.byref(m))
+
+    def mark_snippets(self, mark_type, id=abi.MARK_ANY_ID, before=0, after=0, max_runs_per_log=0xFFFFFFFF):
+        """mark_runs, and for every listed run the text and the span rows of the elements [run_start - before, run_end + after) in one call that keeps the runs
+        on the device (ptx_view_mark_snippets): wire.MarkSnippets.  before == after == 0: the text each run covers."""
+        eng = self.engine
+        m = abi.ptx_mark_snippets()
+        eng._check(eng.lib.ptx_view_mark_snippets(eng.ctx, self.handle, mark_type, id, max_runs_per_log, before, after, C.byref(m)))
+        try:
+            n, k, arr = int(m.n_logs), int(m.n_slices), _copied
+            unit_off, sspan_off = arr(m.unit_off, np.uint64, k + 1), arr(m.sspan_off, np.uint64, k + 1)
+            nr = int(sspan_off[k])
+            return wire.MarkSnippets(status=arr(m.status, np.uint32, n), slice_off=arr(m.run_off, np.uint64, n + 1), elem_start=arr(m.elem_start, np.uint32, k),
+                                     elem_end=arr(m.elem_end, np.uint32, k), unit_off=unit_off, text=arr(m.text, np.uint16, int(unit_off[k])), sspan_off=sspan_off,
+                                     sspans=arr(m.sspans, abi.SPAN_DTYPE, nr), sspan_unit=arr(m.sspan_unit, np.uint32, nr), kernel_ms=float(m.kernel_ms),
+                                     n_runs=arr(m.n_runs, np.uint32, n), run_start=arr(m.run_start, np.uint32, k), run_end=arr(m.run_end, np.uint32, k),
+                                     run_id=arr(m.run_id, np.uint32, k), run_unit=arr(m.run_unit, np.uint32, k), run_len=arr(m.run_len, np.uint32, k),
+                                     match_unit=arr(m.match_unit, np.uint32, k), mark_type=int(m.mark_type))
+        finally:
+            eng.lib.ptx_mark_snippets_free(C.byref(m))
+
+    def find_in_marks(self, pattern, mark_type, id=abi.MARK_ANY_ID, ascii_nocase=False, max_hits_per_log=0xFFFFFFFF):
+        """find_text restricted to the hits whose elements lie inside ONE run of the selector, filtered on the device (ptx_view_find_in_marks): wire.Matches whose
+        n_matches counts the contained hits.  A comment selector needs one id."""
+        eng, pat = self.engine, self._pattern(pattern)
+        m = abi.ptx_matches()
+        eng._check(eng.lib.ptx_view_find_in_marks(eng.ctx, self.handle, pat.ctypes.data_as(abi.u16p), len(pat), abi.FIND_ASCII_NOCASE if ascii_nocase else 0, mark_type, id,
+                                                  max_hits_per_log, C.byref(m)))
+        try:
+            return _matches_of(m)
+        finally:
+            eng.lib.ptx_matches_free(C.byref(m))
+
     def replace_plan(self, pattern, replacement_ids, n_batch_logs, ascii_nocase=False):
         """replaceAll as change() input (ptx_view_replace_plan): per log the matches str.replace would replace — greedy, leftmost, non-overlapping — and, for those
         that cover whole elements, a delete and an insert of the value ids `replacement_ids` (one element each) per match, in descending order, as ONE Change

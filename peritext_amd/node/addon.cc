@@ -105,6 +105,12 @@ struct Lib {
     /* find and replace on a view: hits into change() input */
     ptx_status (*view_replace_plan)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, ptx_replace_plan*) = nullptr;
     void (*replace_plan_free)(ptx_replace_plan*) = nullptr;
+    /* a view queried by format: the runs of a mark, their text, a find inside them */
+    ptx_status (*view_mark_runs)(ptx_ctx*, const ptx_dview*, uint32_t, uint32_t, uint32_t, ptx_mark_runs*) = nullptr;
+    void (*mark_runs_free)(ptx_mark_runs*) = nullptr;
+    ptx_status (*view_mark_snippets)(ptx_ctx*, const ptx_dview*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, ptx_mark_snippets*) = nullptr;
+    void (*mark_snippets_free)(ptx_mark_snippets*) = nullptr;
+    ptx_status (*view_find_in_marks)(ptx_ctx*, const ptx_dview*, const uint16_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, ptx_matches*) = nullptr;
 } L;
 
 #define NAPI_OK(call)                                                        \
@@ -158,7 +164,9 @@ napi_value Open(napi_env env, napi_callback_info info) {
                   sym(L.matches_free, "ptx_matches_free") && sym(L.result_text_slices, "ptx_result_text_slices") && sym(L.slices_free, "ptx_slices_free") &&
                   sym(L.text_view_create, "ptx_text_view_create") && sym(L.text_view_free, "ptx_text_view_free") && sym(L.view_find_text, "ptx_view_find_text") &&
                   sym(L.view_text_slices, "ptx_view_text_slices") && sym(L.view_find_snippets, "ptx_view_find_snippets") && sym(L.snippets_free, "ptx_snippets_free") &&
-                  sym(L.view_replace_plan, "ptx_view_replace_plan") && sym(L.replace_plan_free, "ptx_replace_plan_free");
+                  sym(L.view_replace_plan, "ptx_view_replace_plan") && sym(L.replace_plan_free, "ptx_replace_plan_free") &&
+                  sym(L.view_mark_runs, "ptx_view_mark_runs") && sym(L.mark_runs_free, "ptx_mark_runs_free") && sym(L.view_mark_snippets, "ptx_view_mark_snippets") &&
+                  sym(L.mark_snippets_free, "ptx_mark_snippets_free") && sym(L.view_find_in_marks, "ptx_view_find_in_marks");
         if (!ok) {
             dlclose(L.handle);
             L.handle = nullptr;
@@ -925,6 +933,94 @@ napi_value ViewFindSnippets(napi_env env, napi_callback_info info) {
     L.snippets_free(&m);
     return out;
 }
+/* ---- the view queried by format: viewMarkRuns(ctx, handle, markType, id, maxRunsPerLog) -> {status, nRuns, runOff, runStart, runEnd, runId, runUnit, runLen};
+ *      viewMarkSnippets(ctx, handle, markType, id, maxRunsPerLog, before, after) -> the same and the slice arrays of one slice per listed run (their sliceOff IS
+ *      runOff) with matchUnit; viewFindInMarks(ctx, handle, pattern, flags, markType, id, maxHitsPerLog) -> viewFindText's object, of the contained hits ---- */
+static void runs_to_js(napi_env env, napi_value out, const uint32_t* status, const uint32_t* n_runs, const uint64_t* run_off, const uint32_t* run_start, const uint32_t* run_end,
+                       const uint32_t* run_id, const uint32_t* run_unit, const uint32_t* run_len, size_t nl) {
+    const size_t nr = (size_t)run_off[nl];
+    napi_value v;
+    if ((v = make_u32(env, status, nl))) napi_set_named_property(env, out, "status", v);
+    if ((v = make_u32(env, n_runs, nl))) napi_set_named_property(env, out, "nRuns", v);
+    if ((v = make_typed(env, napi_biguint64_array, 8, run_off, nl + 1))) napi_set_named_property(env, out, "runOff", v);
+    if ((v = make_u32(env, run_start, nr))) napi_set_named_property(env, out, "runStart", v);
+    if ((v = make_u32(env, run_end, nr))) napi_set_named_property(env, out, "runEnd", v);
+    if ((v = make_u32(env, run_id, nr))) napi_set_named_property(env, out, "runId", v);
+    if ((v = make_u32(env, run_unit, nr))) napi_set_named_property(env, out, "runUnit", v);
+    if ((v = make_u32(env, run_len, nr))) napi_set_named_property(env, out, "runLen", v);
+}
+static bool u32_args(napi_env env, const napi_value* argv, uint32_t* out, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (napi_get_value_uint32(env, argv[i], &out[i]) != napi_ok) return false;
+    return true;
+}
+napi_value ViewMarkRuns(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 4 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewMarkRuns(ctx, handle, markType, id, maxRunsPerLog): no live view");
+    uint32_t a[3];
+    if (!u32_args(env, argv + 2, a, 3)) return throw_msg(env, "viewMarkRuns: markType, id and maxRunsPerLog must be unsigned 32-bit numbers");
+    ptx_mark_runs m;
+    const ptx_status st = L.view_mark_runs(ctx, h->view, a[0], a[1], a[2], &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_mark_runs", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        runs_to_js(env, out, m.status, m.n_runs, m.run_off, m.run_start, m.run_end, m.run_id, m.run_unit, m.run_len, (size_t)m.n_logs);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.mark_runs_free(&m);
+    return out;
+}
+napi_value ViewMarkSnippets(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 6 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewMarkSnippets(ctx, handle, markType, id, maxRunsPerLog, before, after): no live view");
+    uint32_t a[5];
+    if (!u32_args(env, argv + 2, a, 5)) return throw_msg(env, "viewMarkSnippets: markType, id, maxRunsPerLog, before and after must be unsigned 32-bit numbers");
+    ptx_mark_snippets m;
+    const ptx_status st = L.view_mark_snippets(ctx, h->view, a[0], a[1], a[2], a[3], a[4], &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_mark_snippets", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        runs_to_js(env, out, m.status, m.n_runs, m.run_off, m.run_start, m.run_end, m.run_id, m.run_unit, m.run_len, (size_t)m.n_logs);
+        cut_to_js(env, out, m.status, (size_t)m.n_logs, (size_t)m.n_slices, m.elem_start, m.elem_end, m.unit_off, m.sspan_off, m.text, m.sspans, m.sspan_unit);
+        if ((v = make_u32(env, m.match_unit, (size_t)m.n_slices))) napi_set_named_property(env, out, "matchUnit", v);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.mark_snippets_free(&m);
+    return out;
+}
+napi_value ViewFindInMarks(napi_env env, napi_callback_info info) {
+    if (!L.handle) return throw_msg(env, "call open(libPath) first");
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ptx_ctx* ctx = argc > 6 ? ctx_of(env, argv[0]) : nullptr;
+    ViewHandle* h = ctx ? view_of(env, argv[1]) : nullptr;
+    if (!h) return throw_msg(env, "viewFindInMarks(ctx, handle, pattern: Uint16Array, flags, markType, id, maxHitsPerLog): no live view");
+    const uint16_t* pat = nullptr;
+    uint32_t np = 0, a[4];
+    if (!pattern_arg(env, argv[2], &pat, &np) || !u32_args(env, argv + 3, a, 4))
+        return throw_msg(env, "viewFindInMarks: pattern must be a Uint16Array, flags, markType, id and maxHitsPerLog unsigned 32-bit numbers");
+    ptx_matches m;
+    const ptx_status st = L.view_find_in_marks(ctx, h->view, pat, np, a[0], a[1], a[2], a[3], &m);
+    if (st != PTX_OK) return lib_error(env, ctx, "ptx_view_find_in_marks", st);
+    napi_value out = nullptr, v;
+    if (napi_create_object(env, &out) == napi_ok) {
+        hits_to_js(env, out, m.status, m.n_matches, m.hit_off, m.hit_unit, m.hit_start, m.hit_end, (size_t)m.n_logs);
+        if (napi_create_double(env, (double)m.kernel_ms, &v) == napi_ok) napi_set_named_property(env, out, "kernelMs", v);
+    }
+    L.matches_free(&m);
+    return out;
+}
 /* viewReplacePlan(ctx, handle, pattern, flags, nReplacement) -> the plan of ptx_view_replace_plan over every log of the view: status, nMatches, nChosen, nReplaced
  * (Uint32Array per log), chgOff, opOff (BigUint64Array), action (Uint8Array), index, count (Uint32Array).  The value ids of the inserts are not the addon's
  * business: index.js writes the replacement's strings into the InputOperations itself, as bridge.ts:445 does */
@@ -1581,7 +1677,10 @@ napi_value Init(napi_env env, napi_value exports) {
                                               {"viewFindText", nullptr, ViewFindText, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"viewTextSlices", nullptr, ViewTextSlices, nullptr, nullptr, nullptr, napi_default, nullptr},
                                               {"viewFindSnippets", nullptr, ViewFindSnippets, nullptr, nullptr, nullptr, napi_default, nullptr},
-                                              {"viewReplacePlan", nullptr, ViewReplacePlan, nullptr, nullptr, nullptr, napi_default, nullptr}};
+                                              {"viewReplacePlan", nullptr, ViewReplacePlan, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewMarkRuns", nullptr, ViewMarkRuns, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewMarkSnippets", nullptr, ViewMarkSnippets, nullptr, nullptr, nullptr, napi_default, nullptr},
+                                              {"viewFindInMarks", nullptr, ViewFindInMarks, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     return exports;
 }

@@ -116,8 +116,20 @@ export interface TextView {
     /** replace all as change() input, planned on the device (ptx_view_replace_plan): the leftmost non-overlapping matches that cover whole elements, in
      *  descending order, a delete and an insert of replacement.split("") each; calls for changeMany = plan.map(logs => logs.map(x => (x.ops.length ? [x.ops] : []))) */
     replacePlan(needle: string, replacement: string, opts?: { asciiNocase?: boolean }): Array<Array<ReplacePlanOfLog>>
+    /** the runs of a mark, chosen on the device (ptx_view_mark_runs): adjacent spans that carry it — for a link: with the same url — are one run; comment runs
+     *  come per id.  A url or id a document does not have gives no runs.  count counts all runs, opts.maxRuns caps the listed ones */
+    markRuns(sel: MarkSelector, opts?: { maxRuns?: number }): Array<Array<{ status: number; count: number; runs: MarkRun[] }>>
+    /** markRuns and, per listed run, its text and formatting with opts.before / opts.after elements of context, in one device call (ptx_view_mark_snippets) */
+    markSnippets(sel: MarkSelector, opts?: { maxRuns?: number; before?: number; after?: number }): Array<Array<{ status: number; count: number; snippets: MarkSnippet[] }>>
+    /** findText restricted to the hits whose elements lie inside one run of `sel` (ptx_view_find_in_marks); a comment selector needs an id */
+    findInMarks(needle: string, sel: MarkSelector, opts?: { ignoreAsciiCase?: boolean; maxHits?: number }): Array<Array<{ status: number; count: number; hits: Array<{ unit: number; startIndex: number; endIndex: number }> }>>
     free(): void
 }
+export type MarkSelector = { type: "strong" | "em" } | { type: "link"; url?: string } | { type: "comment"; id?: string }
+/** [start, end): visible element indexes; unit / length: where the run's text sits in the replica's text (UTF-16 code units) */
+export interface MarkRun { log: number; start: number; end: number; url?: string; id?: string; unit: number; length: number }
+/** text.substr(matchUnit, length) is the run's own text */
+export interface MarkSnippet extends MarkRun { text: string; spans: FormatSpanWithText[]; matchUnit: number }
 export interface ReplacePlanOfLog {
     log: number
     /** the replica's merge / text status, or 5 (PTX_ERR_CAPACITY) where the Change would make more than 65 534 ops: then `ops` is empty */

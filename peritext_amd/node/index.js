@@ -24,6 +24,8 @@ const path = require("path")
 const ACT = { MAKELIST: 0, INSERT: 1, DELETE: 2, ADDMARK: 3, REMOVEMARK: 4, NOP: 5, MAPSET: 6, MAPDEL: 7 }
 const MAPV = { SCALAR: 0, MAP: 1, LIST: 2, DELETED: 3 } /* what a map row writes / ptx_root_entry.kind */
 const MARK_NAMES = ["strong", "em", "comment", "link"] /* schema.ts:125 ALL_MARKS */
+const MARK_ANY_ID = 0xFFFFFFFF /* PTX_MARK_ANY_ID */
+const MARK_NO_ID = 0xFFFFFFFE /* a comment rank no document reaches */
 const SIDE_NAMES = ["before", "after", "startOfText", "endOfText"] /* peritext.ts:17-21 */
 const ATTR = { STRONG: 0x10000000, EM: 0x20000000, LINK: 0x40000000, COMMENT: 0x80000000, ID_MASK: 0x0fffffff }
 const STATUS_MESSAGES = {
@@ -986,6 +988,16 @@ class MergeEngine {
      *                                (for a non-empty replacement) an insert of replacement.split("") at the same index (bridge.ts:425-446); one that starts or
      *                                ends inside a multi-unit element is skipped (nChosen - nReplaced).  opts.asciiNocase as ignoreAsciiCase.  The result is
      *                                ready for changeMany: calls = plan.map(logs => logs.map(x => (x.ops.length ? [x.ops] : [])))
+     *    markRuns(sel, opts)         the runs of a mark, chosen on the device (ptx_view_mark_runs).  sel: { type: "strong" | "em" }, { type: "link", url? } or
+     *                                { type: "comment", id? } — without url / id: every link, every comment; a url or id a document does not have gives no runs.
+     *                                Per document and replica { status, count, runs }, a run being { log, start, end, url | id, unit, length }: the visible
+     *                                element range, the end exclusive, and where its text sits in the replica's text.  Adjacent spans that carry the mark (for a
+     *                                link: the same url) are ONE run; comment runs come per id.  opts.maxRuns caps the listed runs, count counts all
+     *    markSnippets(sel, opts)     markRuns, and per listed run its text and formatting with opts.before / opts.after elements of context (default 0: the text
+     *                                the mark covers — "every comment with the text it is anchored to") in ONE device call: { status, count, snippets }, a
+     *                                snippet being a run and { text, spans, matchUnit } — the run's text starts at text[matchUnit]
+     *    findInMarks(needle, sel, opts)  findText restricted to the hits whose elements lie inside ONE run of sel, filtered on the device; count counts the
+     *                                contained hits.  A comment selector needs an id
      *    free()                      releases the device memory; the view is unusable afterwards */
     textView(docs) {
         const batch = encodeDocs(docs)
@@ -1053,10 +1065,81 @@ class MergeEngine {
                     return { log: l, status: m.status[l], nMatches: m.nMatches[l], nChosen: m.nChosen[l], nReplaced: m.nReplaced[l], ops }
                 }))
             },
+            markRuns(sel, opts) {
+                const s = selArgs(sel), cap = optU32(opts, "maxRuns", 0xFFFFFFFF)
+                const answer = perId(s.ids, id => engine.addon.viewMarkRuns(engine.ctx, live(), s.type, id, cap))
+                let log = 0
+                return docs.map(logs => logs.map(() => {
+                    const l = log++, m = answer(l), runs = []
+                    for (let k = Number(m.runOff[l]); k < Number(m.runOff[l + 1]); k++) runs.push(runOf(s, m, l, k))
+                    return { status: m.status[l], count: m.nRuns[l], runs }
+                }))
+            },
+            markSnippets(sel, opts) {
+                const s = selArgs(sel), cap = optU32(opts, "maxRuns", 0xFFFFFFFF), before = optU32(opts, "before", 0), after = optU32(opts, "after", 0)
+                const answer = perId(s.ids, id => engine.addon.viewMarkSnippets(engine.ctx, live(), s.type, id, cap, before, after))
+                let log = 0
+                return docs.map(logs => logs.map(() => {
+                    const l = log++, m = answer(l), snippets = []
+                    for (let k = Number(m.runOff[l]); k < Number(m.runOff[l + 1]); k++) {
+                        const cut = sliceOf(batch, rows, m, l, k)
+                        snippets.push(Object.assign(runOf(s, m, l, k), { text: cut.text, spans: cut.spans, matchUnit: m.matchUnit[k] }))
+                    }
+                    return { status: m.status[l], count: m.nRuns[l], snippets }
+                }))
+            },
+            findInMarks(needle, sel, opts) {
+                const a = findArgs(needle, opts), s = selArgs(sel)
+                if (s.type === MARK_NAMES.indexOf("comment") && sel.id === undefined) throw new RangeError("sel.id: a find inside comments needs one comment id")
+                const answer = perId(s.ids, id => engine.addon.viewFindInMarks(engine.ctx, live(), a.pattern, a.flags, s.type, id, a.maxHits))
+                let log = 0
+                return docs.map(logs => logs.map(() => hitsOfLog(answer(log), log++)))
+            },
             free() {
                 if (handle !== null) engine.addon.viewFree(engine.ctx, handle)
                 handle = null
             },
+        }
+        /* a selector as the C ABI's (mark_type, id), the id per log: a url has ONE id in the batch's table, a comment id its rank in its OWN document — the
+         * tables the codec keeps —; a url or id a document does not have becomes an id nothing has: no runs, not an error */
+        function selArgs(sel) {
+            const type = sel && typeof sel === "object" ? MARK_NAMES.indexOf(sel.type) : -1
+            if (type < 0) throw new RangeError('sel.type: "strong", "em", "link" or "comment"')
+            let idOf = () => MARK_ANY_ID
+            if (sel.type === "link" && sel.url !== undefined) {
+                if (typeof sel.url !== "string") throw new TypeError("sel.url: a string")
+                const at = batch.urls.indexOf(sel.url)
+                idOf = () => (at < 0 ? batch.urls.length : at)
+            } else if (sel.type === "comment" && sel.id !== undefined) {
+                if (typeof sel.id !== "string") throw new TypeError("sel.id: a string")
+                idOf = l => {
+                    const at = batch.docComments[batch.logDoc[l]].indexOf(sel.id)
+                    return at < 0 ? MARK_NO_ID : at
+                }
+            }
+            return { type, name: sel.type, ids: batch.logDoc.map((_, l) => idOf(l)) }
+        }
+        /* one device call per distinct id (a comment id may have another rank in another document); log l reads the answer made with ITS id */
+        function perId(ids, call) {
+            const made = new Map()
+            if (ids.length === 0) made.set(MARK_ANY_ID, call(MARK_ANY_ID)) /* (no logs: the argument checks still run) */
+            return l => {
+                if (!made.has(ids[l])) made.set(ids[l], call(ids[l]))
+                return made.get(ids[l])
+            }
+        }
+        function optU32(opts, name, dflt) {
+            const v = opts && opts[name] !== undefined ? opts[name] : dflt
+            if (!Number.isInteger(v) || v < 0 || v > 0xFFFFFFFF) throw new RangeError(name + ": an unsigned 32-bit integer")
+            return v
+        }
+        function runOf(s, m, l, k) {
+            const run = { log: l, start: m.runStart[k], end: m.runEnd[k] }
+            if (s.name === "link") run.url = batch.urls[m.runId[k]]
+            if (s.name === "comment") run.id = batch.docComments[batch.logDoc[l]][m.runId[k]]
+            run.unit = m.runUnit[k]
+            run.length = m.runLen[k]
+            return run
         }
     }
     /** Per-document digests (2 x u64 as BigInt pairs) of every log: equal digests <=> deep-equal spans. */

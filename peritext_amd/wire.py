@@ -953,6 +953,61 @@ class Snippets(Slices):
         return [(int(self.hit_unit[k]), int(self.hit_start[k]), int(self.hit_end[k]), self.of_slice(k), int(self.match_unit[k])) for k in range(a, b)]
 
 
+@dataclass
+class MarkRuns:
+    """Host view of ptx_mark_runs (TextView.mark_runs): n_runs[l] counts ALL runs of the selector in log l; its listed runs — the first max_runs_per_log — are the
+    rows run_off[l] .. run_off[l + 1] of run_start / run_end (visible element indexes, the end exclusive), run_id (0, the url id, or the doc-local comment id),
+    run_unit (code-unit offset within the log's text) and run_len (code units).  Strong, em and link runs ascend by start; comment runs come in the result's own
+    order (id, start)."""
+
+    status: np.ndarray  # u32 [n_logs] exactly Matches.status of the view
+    n_runs: np.ndarray  # u32 [n_logs]
+    run_off: np.ndarray  # u64 [n_logs + 1]
+    run_start: np.ndarray  # u32 [run_off[n_logs]]
+    run_end: np.ndarray
+    run_id: np.ndarray
+    run_unit: np.ndarray
+    run_len: np.ndarray
+    mark_type: int = 0
+    kernel_ms: float = 0.0
+
+    def of_log(self, log):
+        """[(start, end, id, unit, length)] of one log's listed runs."""
+        a, b = int(self.run_off[log]), int(self.run_off[log + 1])
+        return [(int(self.run_start[k]), int(self.run_end[k]), int(self.run_id[k]), int(self.run_unit[k]), int(self.run_len[k])) for k in range(a, b)]
+
+
+@dataclass
+class MarkSnippets(Slices):
+    """Host view of ptx_mark_snippets (TextView.mark_snippets): the runs of a MarkRuns and one slice per listed run, in run order — slice_off IS run_off.  The slice
+    of run k is [run_start[k] - before, run_end[k] + after), saturated and clamped; match_unit[k] is the code-unit offset of the run's first unit within snippet
+    k's text.  decode_slice_spans takes it as it takes a Slices."""
+
+    n_runs: np.ndarray = None  # u32 [n_logs]
+    run_start: np.ndarray = None  # u32 [n_slices]
+    run_end: np.ndarray = None
+    run_id: np.ndarray = None
+    run_unit: np.ndarray = None
+    run_len: np.ndarray = None
+    match_unit: np.ndarray = None
+    mark_type: int = 0
+
+    @property
+    def run_off(self):
+        return self.slice_off
+
+    def runs(self):
+        """The run half as a MarkRuns."""
+        return MarkRuns(status=self.status, n_runs=self.n_runs, run_off=self.slice_off, run_start=self.run_start, run_end=self.run_end, run_id=self.run_id,
+                        run_unit=self.run_unit, run_len=self.run_len, mark_type=self.mark_type, kernel_ms=self.kernel_ms)
+
+    def of_log(self, log):
+        """[(start, end, id, unit, length, snippet text, match_unit)] of one log's listed runs."""
+        a, b = int(self.slice_off[log]), int(self.slice_off[log + 1])
+        return [(int(self.run_start[k]), int(self.run_end[k]), int(self.run_id[k]), int(self.run_unit[k]), int(self.run_len[k]), self.of_slice(k), int(self.match_unit[k]))
+                for k in range(a, b)]
+
+
 def decode_slice_spans(batch, res, slices, log, j):
     """FormatSpanWithText[] of slice j of log `log`: what cutting decode_spans_text's result down to the slice's elements gives — every row's text ONE slice of
     the slice's text, comment ids resolved against `res`'s cintervals at the row's (document) start.  `res` and `slices` cover the same range of logs."""
